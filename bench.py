@@ -3,7 +3,7 @@
 at BASELINE.json's metric point -- Yarn-Llama-2-7B shapes (32 layers, 32 heads, D=128, fp16),
 seqlen 32768, token budget 2048 = 128 pages of 16 -- on N GPUs of one node.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config {2,3,4,5}]
+    python bench.py [--gpus N --steps K --warmup W] [--config {2,3,4,5}] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
 ``--gpus N`` with N > 1 and no WORLD_SIZE in the environment makes this process a LAUNCHER: it starts N
@@ -19,9 +19,11 @@ with one RCCL all_gather of the sampled token ids (weak scaling: the same sequen
 over RCCL, world size 1: +1 % per step; issuing the gather asynchronously behind the next step was
 tried and is slower, +16 % -- the RCCL kernel then runs beside the step's kernels.)
 
-One JSON line on stdout (rank 0).  Extra objects: "roofline" (the dominant kernel OF THE TIMED STEP:
+One JSON line on stdout (rank 0).  A plain run sets up, warms up, times K steps and prints the headline (`value`,
+`ms_per_step`); `--dump-outputs DIR` also writes the last timed step's attention outputs.  `--full` adds everything
+else, measured after the headline.  Extra objects of --full: "roofline" (the dominant kernel OF THE TIMED STEP:
 sparse_decode_kernel with its top-k front end; algorithmic bytes / HIP-event launch time) and
-"cpu_baseline" (oracle/torch_ref eager port timed on the host cores, bounded sample).  Side objects of the default N = 1 run,
+"cpu_baseline" (oracle/torch_ref eager port timed on the host cores, bounded sample).  Side objects of the --full N = 1 run,
 measured after the headline and outside `value`: "batched_8seq", "cfg5_8seq_gqa" (8 sequences per GPU), the same and the
 headline on the reference's NHD pool layout ("reference_layout_nhd", "batched_8seq_nhd", "cfg5_8seq_gqa_nhd": the default
 layout is this build's row-rotated NHD since round 6, config.kv_layout) and
@@ -114,13 +116,21 @@ def parse(argv=None):
                          "alone at seqlen 4096 x budgets 64-512 and 32768 x 256/640/896, top-k and estimate at the six "
                          "LongBench pairs of scripts/bench_kernels.sh) -> gpurun_out/kernel_sweep.json + a markdown table")
     ap.add_argument("--no-side", action="store_true",
-                    help="skip the side configurations (8 sequences per GPU) the default headline run measures after its "
+                    help="skip the side configurations (8 sequences per GPU) the --full headline run measures after its "
                          "timed region")
     ap.add_argument("--side-steps", type=int, default=100, help="timed steps of each side configuration")
     ap.add_argument("--side-warmup", type=int, default=None,
                     help="untimed steps before each side configuration's timed steps (default: max(--warmup, 20))")
     ap.add_argument("--cpu-sample-s", type=float, default=15.0)
     ap.add_argument("--seed", type=int, default=0, help="seed of the synthetic K/V/q (SURVEY 8d: seeds 0, 1, 2)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, measure everything else: per-operator times and the roofline object, the "
+                         "reference op sequence, the CPU baseline, the side configurations, the prefill operator and (N > 1) "
+                         "the rerun without the token gather.  Without it a run sets up, warms up, times --steps steps and "
+                         "prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (the attention output of every "
+                         "layer and local sequence) as DIR/<name>.npy in float32")
     a = ap.parse_args(argv)
     preset = CONFIGS[a.config]
     custom = []
@@ -656,6 +666,37 @@ def add_traffic(roof, a, n_local):
                                 "run on one XCD (XCD-aware grid order) and re-read each other's pages from its L2")
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ws, rank, stub):
+    """--dump-outputs: what the last timed step computed, as a caller of the step receives it -- the attention output of every
+    layer for every local sequence, `attn_out.npy` = [layers, sequences, heads, head_dim] in float32 (the stub: its state,
+    float64).  Rank r > 0 writes `<name>_rank<r>.npy`.  Above 64 MB in all, each array is written as a fixed sample of its
+    flattened elements (positions drawn with seed 0, in increasing order)."""
+    import numpy as np
+    import torch
+
+    if stub:
+        arrays = {"stub_state": torch.stack([wl.x for wl in ws]).double()}
+    else:
+        per_seq = []
+        for wl in ws:
+            if isinstance(wl, BatchedWorkload):
+                per_seq.append(wl.o.float())  # [layers, n, H, D]: the buffers the batched layers write
+            else:
+                per_seq.append(torch.stack([o.reshape(1, *o.shape[-2:]) for o in wl.outs]).float())  # [layers, 1, H, D]
+        arrays = {"attn_out": torch.cat(per_seq, dim=1)}
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(t.numel() * t.element_size() for t in arrays.values())
+    for name, t in arrays.items():
+        x = t.cpu().numpy()
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, x.size * DUMP_LIMIT_BYTES // total)
+            x = x.reshape(-1)[np.sort(np.random.default_rng(0).choice(x.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ("" if rank == 0 else f"_rank{rank}") + ".npy"), x)
+
+
 def measure(a, dev, dist, world_seen, rank, stub, side=False):
     """Build the workload `a` describes, capture the step, time EXACTLY a.steps steps after a.warmup (barrier +
     synchronize on both sides, max over ranks) and, on rank 0, return the result line as a dict (None elsewhere).
@@ -763,11 +804,13 @@ def measure(a, dev, dist, world_seen, rank, stub, side=False):
 
     ms_per_step = elapsed * 1e3 / a.steps
     value = world_seen * n_local * a.steps / elapsed  # one token per local sequence per step
+    if a.dump_outputs and not side:  # before anything else launches into the step's output buffers
+        dump_outputs(a.dump_outputs, ws, rank, stub)
 
     # side figure for N > 1 ("report both with and without the gather"): the same K steps again
     # without the all_gather of token ids; not part of `value`
     ms_no_gather = None
-    if dist is not None:
+    if dist is not None and a.full:
         sync()
         dist.barrier()
         t1 = time.perf_counter()
@@ -816,15 +859,16 @@ def measure(a, dev, dist, world_seen, rank, stub, side=False):
         if not stub:
             ctl0 = w.ctl.seqs[0] if batched else w.ctl
             out["config"]["seqlen_after_run"] = ctl0.kv_cache.seqlen
-            if w.dyn and not w.dense:
+            out["roofline"] = None  # the per-operator measurements below take runs of their own: --full only
+            if a.full and w.dyn and not w.dense:
                 ops, roof = step_op_times(w, a, bpl)
                 add_traffic(roof, a, n_local)
                 out["roofline"], out["ops_us"] = roof, ops
             dense_us = None
-            if not side:
+            if a.full and not side:
                 ref_ops, dense_us = reference_op_times(w, a, bpl)
                 out["reference_op_sequence_us"] = ref_ops
-            if w.dense and w.dyn and not batched:  # full-KV config: the dense kernel IS the dominant kernel of the timed step
+            if a.full and w.dense and w.dyn and not batched:  # full-KV config: the dense kernel IS the dominant kernel of the timed step
                 ctl0.begin_graph_decode(dense_layers=True)  # (reference_op_times re-planned the handlers)
                 hd = ctl0._dense_handler
                 od = [w.q[l].clone() for l in range(a.layers)]
@@ -863,7 +907,7 @@ def measure(a, dev, dist, world_seen, rank, stub, side=False):
                 out["speedup_vs_dense"] = dense_us / us_per_seq_layer
             if "ops_us" in out and "batched_dense_full_kv_us_per_sequence" in out["ops_us"]:
                 out["speedup_vs_batched_dense"] = out["ops_us"]["batched_dense_full_kv_us_per_sequence"] / us_per_seq_layer
-            if world_seen == 1 and not a.no_cpu_baseline and not side:
+            if a.full and world_seen == 1 and not a.no_cpu_baseline and not side:
                 out["cpu_baseline"] = cpu_baseline(a, w, a.cpu_sample_s)
             else:
                 out["cpu_baseline"] = None
@@ -972,7 +1016,7 @@ def main():
         torch.cuda.set_device(dev)
     out = measure(a, dev, dist, world_seen, rank, stub)
 
-    # ---- side configurations, measured AFTER the headline and outside `value` (the headline stays cfg 3 x 1 sequence per
+    # ---- side configurations (--full), measured AFTER the headline and outside `value` (the headline stays cfg 3 x 1 sequence per
     # GPU so that N = 1 equals BENCH): where the fixed costs of a launch are shared by 8 sequences per GPU -- the per-GPU
     # load of BASELINE configs[4].  N = 1: the headline shapes x 8 sequences (MHA) and configs[4]'s per-GPU load (GQA).
     # N > 1: EVERY rank runs configs[4]'s per-GPU load with the per-step all_gather of its 8 token
@@ -980,7 +1024,7 @@ def main():
     # aggregate tokens/s and per-GPU chain fraction.  A failure here must not cost the headline line: it is printed in
     # any case.
     try:
-        if (a.config == 3 and not a.no_side and "custom" not in a.workload_label and a.mode == "graph"):
+        if (a.full and a.config == 3 and not a.no_side and "custom" not in a.workload_label and a.mode == "graph"):
             import gc
 
             sides = [("batched_8seq", dict(config=3, seqs_per_gpu=8)), ("cfg5_8seq_gqa", dict(config=5))]
@@ -998,7 +1042,7 @@ def main():
                     torch.cuda.empty_cache()
                 side_warmup = a.side_warmup if a.side_warmup is not None else max(a.warmup, 20)
                 a2 = parse(["--config", str(overrides["config"]), "--steps", str(a.side_steps), "--warmup", str(side_warmup),
-                            "--seed", str(a.seed), "--no-cpu-baseline", "--gpus", str(a.gpus),
+                            "--seed", str(a.seed), "--no-cpu-baseline", "--gpus", str(a.gpus), "--full",
                             "--layer-launches", a.layer_launches, "--layout", overrides.get("layout", a.layout)]
                            + (["--seqs-per-gpu", str(overrides["seqs_per_gpu"])] if "seqs_per_gpu" in overrides else []))
                 try:
@@ -1046,7 +1090,7 @@ def main():
                                 "tokens_per_s is the aggregate over all ranks, the fractions are per GPU (rank 0's)"
                                 if dist is not None else "")),
                 }
-        if (dist is None and out is not None and not stub and not a.no_side and a.config == 3
+        if (a.full and dist is None and out is not None and not stub and not a.no_side and a.config == 3
                 and "custom" not in a.workload_label):
             try:
                 out["prefill_attention"] = prefill_side(a, dev)

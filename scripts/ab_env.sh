@@ -2,6 +2,7 @@
 # A/B of tuning environment variables on one box (QUEST_TUNING=1 is set): each "NAME=VAL[,NAME=VAL]" set runs the bench once.
 # usage: scripts/ab_env.sh <tag> "<bench args>" <set> [<set> ...]      (set "-" = no variable)
 tag=$1; args=$2; shift 2
+args="--full $args"  # the roofline / speed-up figures printed below are measured by --full
 export QUEST_TUNING=1
 for set in "$@"; do
   name=$(echo "$set" | tr ',=/' '___' | tail -c 60)

@@ -12,5 +12,5 @@ except Exception as e:
     print(sys.argv[2], "FAILED", e, flush=True)
 PY
 done; done; }
-run product python bench.py
-for v in i8 w8 w2; do run variant_$v env QUEST_HIP_LIB=$PWD/quest_amd/libquest_hip_est_$v.so python bench.py; done
+run product python bench.py --full
+for v in i8 w8 w2; do run variant_$v env QUEST_HIP_LIB=$PWD/quest_amd/libquest_hip_est_$v.so python bench.py --full; done

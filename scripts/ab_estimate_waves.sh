@@ -13,5 +13,5 @@ except Exception as e:
     print(sys.argv[2], "FAILED", e, flush=True)
 PY
 done; done; }
-run product python bench.py
-run variant_w2 env QUEST_HIP_LIB=$PWD/quest_amd/libquest_hip_est_w2.so python bench.py
+run product python bench.py --full
+run variant_w2 env QUEST_HIP_LIB=$PWD/quest_amd/libquest_hip_est_w2.so python bench.py --full

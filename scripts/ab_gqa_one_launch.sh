@@ -12,7 +12,7 @@ except Exception as e:
     print(sys.argv[2], "FAILED", e, flush=True)
 PY
 done; }
-B="python bench.py --config 5 --steps 200 --warmup 20 --no-side --no-cpu-baseline"
+B="python bench.py --full --config 5 --steps 200 --warmup 20 --no-side --no-cpu-baseline"
 run two_launches $B --layer-launches two
 run one_launch $B --layer-launches one
 for v in c q 8 16; do

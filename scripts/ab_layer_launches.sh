@@ -7,7 +7,7 @@ mkdir -p gpurun_out
 for c in $cfgs; do
   for form in two one; do
     if [ "$c" = "3x8" ]; then args="--config 3 --seqs-per-gpu 8"; else args="--config $c"; fi
-    timeout -k 10 400 python bench.py $args --steps 100 --no-cpu-baseline --no-side --layer-launches $form \
+    timeout -k 10 400 python bench.py --full $args --steps 100 --no-cpu-baseline --no-side --layer-launches $form \
       > gpurun_out/${tag}_cfg${c}_${form}.json 2> gpurun_out/${tag}_cfg${c}_${form}.err
     python - <<PY
 import json

@@ -6,7 +6,7 @@ layouts=${@:-NHD NHD_ROT}
 run() {  # name, bench args
   for rep in 1 2; do for lay in $layouts; do
     f=gpurun_out/${tag}_$1_${lay}_$rep.json
-    timeout -k 10 400 python bench.py $2 --layout $lay --no-cpu-baseline --no-side > $f 2> ${f%.json}.err
+    timeout -k 10 400 python bench.py --full $2 --layout $lay --no-cpu-baseline --no-side > $f 2> ${f%.json}.err
     python - <<PY
 import json
 try:

@@ -1,15 +1,15 @@
 #!/bin/bash
-# Closing measurements of a round on ONE box: the default bench line (side objects + CPU baseline), the driver's command,
+# Closing measurements of a round on ONE box: the --full bench line (side objects + CPU baseline), the driver's command,
 # the other configurations, then rocprofv3 kernel stats + PMC traffic per configuration and profiles/traffic_latest.json.
 #   scripts/final_round.sh r05 [lines|profiles|e2e]      (default: lines + profiles)
 set -o pipefail
 R=${1:-r05}; what=${2:-all}
 O=$PWD/gpurun_out; mkdir -p $O
 if [ "$what" = all ] || [ "$what" = lines ]; then
-  python bench.py > $O/${R}_bench_line_default.json 2> $O/${R}_bench_line_default.err || { tail -5 $O/${R}_bench_line_default.err; exit 1; }
-  python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench_line_driver.json 2> $O/${R}_bench_line_driver.err || exit 1
-  for c in 2 4 5; do python bench.py --config $c --no-side > $O/${R}_bench_line_cfg$c.json 2> $O/${R}_bench_line_cfg$c.err || { tail -5 $O/${R}_bench_line_cfg$c.err; exit 1; }; done
-  python bench.py --config 3 --seqs-per-gpu 8 --no-side > $O/${R}_bench_line_cfg3x8.json 2> $O/${R}_bench_line_cfg3x8.err || exit 1
+  python bench.py --full > $O/${R}_bench_line_default.json 2> $O/${R}_bench_line_default.err || { tail -5 $O/${R}_bench_line_default.err; exit 1; }
+  python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/${R}_bench_line_driver.json 2> $O/${R}_bench_line_driver.err || exit 1
+  for c in 2 4 5; do python bench.py --full --config $c --no-side > $O/${R}_bench_line_cfg$c.json 2> $O/${R}_bench_line_cfg$c.err || { tail -5 $O/${R}_bench_line_cfg$c.err; exit 1; }; done
+  python bench.py --full --config 3 --seqs-per-gpu 8 --no-side > $O/${R}_bench_line_cfg3x8.json 2> $O/${R}_bench_line_cfg3x8.err || exit 1
 fi
 if [ "$what" = all ] || [ "$what" = profiles ]; then
   for t in "cfg3:--config 3" "cfg3x8:--config 3 --seqs-per-gpu 8" "cfg5:--config 5" "cfg4:--config 4" "cfg2:--config 2"; do

@@ -3,8 +3,8 @@
 set -e
 tag=${SQ_TAG:-sq}; out=gpurun_out/prof_$tag; rm -rf $out; mkdir -p $out  # SQ_TAG / QUEST_HIP_LIB select a build variant
 cd /tmp 2>/dev/null && export TMPDIR=/tmp && cd - >/dev/null
-rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS --output-format csv -d $out/a -o r -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-dense "$@" > /dev/null 2> $out/a.err
-rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --output-format csv -d $out/b -o r -- python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-dense "$@" > /dev/null 2> $out/b.err
+rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_VALU SQ_INSTS_LDS --output-format csv -d $out/a -o r -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-dense "$@" > /dev/null 2> $out/a.err
+rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_SMEM SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --output-format csv -d $out/b -o r -- python3 bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-dense "$@" > /dev/null 2> $out/b.err
 python3 - <<PY
 import csv, glob, statistics, json
 from collections import defaultdict

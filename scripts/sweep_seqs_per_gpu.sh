@@ -5,7 +5,7 @@
 R=${1:-r05}
 O=gpurun_out/${R}_seqs_per_gpu_sweep.jsonl; mkdir -p gpurun_out; : > $O
 for n in 1 2 3 4 5 6 8 12 16; do
-  timeout -k 10 300 python bench.py --seqs-per-gpu $n --steps 100 --warmup 10 --no-side --no-cpu-baseline 2> gpurun_out/${R}_sweep_$n.err | grep '^{' >> $O || { tail -3 gpurun_out/${R}_sweep_$n.err; exit 1; }
+  timeout -k 10 300 python bench.py --full --seqs-per-gpu $n --steps 100 --warmup 10 --no-side --no-cpu-baseline 2> ${O%.jsonl}_$n.err | grep '^{' >> $O || { tail -3 ${O%.jsonl}_$n.err; exit 1; }
 done
 python3 - "$O" <<'PY'
 import json, sys

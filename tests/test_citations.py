@@ -1,8 +1,9 @@
 """Every `file:line` citation of the boundary documents resolves against the reference tree.
 
 `include/quest_hip.h` and `INTEGRATION.md` tell a maintainer which reference declaration each C-ABI entry replaces.  A
-citation that points at the wrong lines is worse than none, and nobody re-reads them by hand: this test does, whenever
-`/root/reference` is present (the build container; it is skipped on the GPU box, where the reference does not exist).
+citation that points at the wrong lines is worse than none, and nobody re-reads them by hand: this test does, against
+tests/golden/reference_citations.json -- the cited reference files' paths, line counts and the lines each pinned identifier
+occurs on, recorded from a reference checkout by tests/golden/make_citations_golden.py (rerun it after changing a citation).
 
 Checked for every citation `path/file.ext:A` or `:A-B` (and the `:C-D` continuations that follow it):
   * the file exists in the reference tree (by its path suffix; a bare basename must be unique or one candidate must fit),
@@ -10,16 +11,15 @@ Checked for every citation `path/file.ext:A` or `:A-B` (and the `:C-D` continuat
 and, where the text names the symbol the citation is about -- `symbol (file:A-B`, `-> Symbol, file:A-B` --
   * that symbol occurs inside the cited lines.
 """
+import json
 import os
 import re
 
 import pytest
 
-REF = "/root/reference"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "reference_citations.json")
 DOCS = ["include/quest_hip.h", "INTEGRATION.md", "examples/pybind_binding.cpp"]
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason="the reference tree is only present in the build container")
 
 CITE = re.compile(r"(?P<path>(?:[\w.-]+/)*[\w-]+\.(?:cuh|cu|h|py|sh|md|cmake|txt)):(?P<a>\d+)(?:-(?P<b>\d+))?")
 CONT = re.compile(r"\s*(?:,|/|and|kernel|launch|math|planner|aux|dispatch)?\s*:(\d+)(?:-(\d+))?")
@@ -32,25 +32,30 @@ OWN_FILES = {"quest_hip.h", "INTEGRATION.md", "DESIGN.md", "SURVEY.md", "BASELIN
 
 
 def _index():
+    """basename -> [(path in the reference tree, its record: line count + the lines each pinned identifier occurs on)]"""
+    with open(FIXTURE) as f:
+        recorded = json.load(f)["files"]
     files = {}
-    for d, _, names in os.walk(REF):
-        if "/.git" in d:
-            continue
-        for n in names:
-            files.setdefault(n, []).append(os.path.join(d, n))
+    for rel, rec in recorded.items():
+        files.setdefault(os.path.basename(rel), []).append(("/" + rel, rec))
     return files
 
 
 def _candidates(index, path):
     base = os.path.basename(path)
-    return [f for f in index.get(base, []) if f.endswith("/" + path) or "/" not in path]
+    return [f for f in index.get(base, []) if f[0].endswith("/" + path) or "/" not in path]
 
 
-def _lines(path, cache={}):
-    if path not in cache:
-        with open(path, errors="replace") as f:
-            cache[path] = f.read().splitlines()
-    return cache[path]
+def _n_lines(cand):
+    return cand[1]["lines"]
+
+
+def _occurs(cand, symbol, a=1, b=None):
+    """Does `symbol` occur on a line of the range a..b of the file (whole file: b None)?  An identifier the fixture does
+    not record for the file fails the test: rerun tests/golden/make_citations_golden.py."""
+    lines = cand[1]["symbols"].get(symbol)
+    assert lines is not None, f"{cand[0]}: `{symbol}` not recorded in {os.path.relpath(FIXTURE, ROOT)}"
+    return any(a <= n <= (b if b is not None else n) for n in lines)
 
 
 def _citations(text):
@@ -88,22 +93,22 @@ def test_every_citation_resolves_and_names_its_symbol(doc):
         if not cands:
             problems.append(f"{doc}:{line_no}: {path}:{a}-{b}: no such file in the reference")
             continue
-        fits = [c for c in cands if 1 <= a <= b <= len(_lines(c))]
+        fits = [c for c in cands if 1 <= a <= b <= _n_lines(c)]
         if not fits:
-            problems.append(f"{doc}:{line_no}: {path}:{a}-{b}: outside the file ({[len(_lines(c)) for c in cands]} lines)")
+            problems.append(f"{doc}:{line_no}: {path}:{a}-{b}: outside the file ({[_n_lines(c) for c in cands]} lines)")
             continue
         n_checked += 1
         # a code identifier (snake_case or CamelCase), not the English word that happens to precede a parenthesis
         if symbol and ("_" in symbol or re.search(r"[a-z][A-Z]", symbol)) and not symbol.isupper():
             plain = symbol.split("::")[-1]
-            hit = any(plain in "\n".join(_lines(c)[a - 1:b]) for c in fits)
+            hit = any(_occurs(c, plain, a, b) for c in fits)
             # only symbols the reference file knows at all are pinned to the range (the sentence may name one of OUR
             # functions in front of a citation that explains it)
-            known = any(plain in "\n".join(_lines(c)) for c in fits)
+            known = any(_occurs(c, plain) for c in fits)
             if known:
                 n_symbols += 1
                 if not hit:
-                    where = [i + 1 for c in fits for i, l in enumerate(_lines(c)) if plain in l][:6]
+                    where = [n for c in fits for n in c[1]["symbols"][plain]][:6]
                     problems.append(f"{doc}:{line_no}: `{plain}` is not inside {path}:{a}-{b} (it occurs at lines {where})")
     assert not problems, "\n".join(problems)
     assert n_checked >= EXPECT[doc][0] and n_symbols >= EXPECT[doc][1], (n_checked, n_symbols)

@@ -76,7 +76,7 @@ def test_bench_launcher_starts_n_ranks_and_reports_world_size():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["QUEST_BENCH_STUB"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-                        "--config", "5"], env=env, capture_output=True, text=True, timeout=600)
+                        "--config", "5", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -94,7 +94,7 @@ def test_bench_launcher_starts_n_ranks_and_reports_world_size():
 
 
 def test_bench_default_headline_reports_configs4_side_measurement_under_n_ranks():
-    """under N > 1 the default (cfg 3) headline run must ALSO measure BASELINE configs[4]'s shape -- 8 GQA
+    """under N > 1 the --full (cfg 3) headline run must ALSO measure BASELINE configs[4]'s shape -- 8 GQA
     sequences per GPU on every rank, each step ending with the all_gather of the token ids -- and report it as a side
     object (aggregate tokens/s over all ranks); the headline itself stays one cfg-3 sequence per GPU."""
     import json
@@ -105,7 +105,7 @@ def test_bench_default_headline_reports_configs4_side_measurement_under_n_ranks(
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env["QUEST_BENCH_STUB"] = "1"
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "4", "--warmup", "1",
-                        "--side-steps", "3"], env=env, capture_output=True, text=True, timeout=600)
+                        "--side-steps", "3", "--full"], env=env, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -132,7 +132,7 @@ def test_bench_launcher_at_the_width_the_driver_uses_world_size_8():
     env["QUEST_BENCH_STUB"] = "1"
     env["OMP_NUM_THREADS"] = "1"  # 8 ranks on the 8 cores of the build container
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "8", "--steps", "3", "--warmup", "1",
-                        "--side-steps", "2"], env=env, capture_output=True, text=True, timeout=900)
+                        "--side-steps", "2", "--full"], env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -160,7 +160,7 @@ def test_bench_side_measurement_that_one_rank_cannot_build_leaves_every_rank_tog
     env["QUEST_BENCH_STUB_BUILD_FAIL"] = "1:1"  # rank 1, in the side measurement
     t0 = time.time()
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--side-steps", "2"], env=env, capture_output=True, text=True, timeout=300)
+                        "--side-steps", "2", "--full"], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     assert time.time() - t0 < 60
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -214,7 +214,7 @@ def test_bench_launcher_reports_a_failing_rank0():
 
 def test_bench_default_single_gpu_line_names_its_pool_layout_and_carries_the_nhd_figures_beside_it():
     """Round 6: the default pool layout of bench.py is this build's row-rotated NHD.  The line says so (config.kv_layout) and
-    the default N = 1 run measures the headline and both 8-sequence side configurations on the REFERENCE's NHD pool as
+    the --full N = 1 run measures the headline and both 8-sequence side configurations on the REFERENCE's NHD pool as
     well (a headline on another layout carries the NHD figure beside it); `--layout NHD` runs the reference's
     layout and needs no such objects.  CPU stub: the control flow and the JSON contract, not the numbers."""
     import json
@@ -227,7 +227,7 @@ def test_bench_default_single_gpu_line_names_its_pool_layout_and_carries_the_nhd
 
     def run(*extra):
         r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "1", "--side-steps", "3",
-                            "--no-cpu-baseline", *extra], env=env, capture_output=True, text=True, timeout=600)
+                            "--no-cpu-baseline", "--full", *extra], env=env, capture_output=True, text=True, timeout=600)
         assert r.returncode == 0, r.stderr[-2000:]
         lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
         assert len(lines) == 1 and r.stdout.strip() == lines[0], r.stdout
@@ -265,3 +265,42 @@ def test_bench_config_labels_follow_the_arguments():
     b = bench.bytes_per_layer(bench.parse(["--config", "3"]))
     assert b["attn"] == 128 * 16 * 2 * 32 * 128 * 2 + 32 * 128 * 2 + 32 * 127 * 4 + 32 * 128 * 2 and b["sparse"]
     assert not bench.bytes_per_layer(bench.parse(["--config", "2"]))["sparse"]
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) sets up, warms up, times exactly --steps steps and prints the headline line: no side
+    configurations, no CPU baseline, no per-operator or N > 1 rerun figures.  --dump-outputs writes what the last timed
+    step computed, identically from run to run.  CPU stub: the stub's state counts the steps it took."""
+    import json
+    import subprocess
+    import sys
+
+    import numpy as np
+
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
+    env["QUEST_BENCH_STUB"] = "1"
+
+    def run(d, *extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "5", "--warmup", "2",
+                            "--dump-outputs", str(d), *extra], env=env, capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1 and r.stdout.strip() == lines[0], r.stdout
+        return json.loads(lines[0])
+
+    a, b = tmp_path / "a", tmp_path / "b"
+    out = run(a)
+    for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert key in out, key
+    assert out["steps"] == 5 and out["warmup"] == 2 and out["unit"] == "tokens/s" and out["higher_is_better"] is True
+    assert abs(out["value"] - 5 / (out["ms_per_step"] * 5e-3)) / out["value"] < 1e-6
+    assert not any(k in out for k in ("batched_8seq", "cfg5_8seq_gqa", "reference_layout_nhd", "prefill_attention",
+                                      "reference_op_sequence_us", "ops_us"))
+    assert out["cpu_baseline"] is None and out["roofline"] is None and out["ms_per_step_without_token_gather"] is None
+    x = np.load(os.path.join(a, "stub_state.npy"))
+    assert x.dtype == np.float64 and np.all(x == 2 + 5)  # warm-up + timed steps, one increment each
+    run(b)
+    assert np.array_equal(np.load(os.path.join(b, "stub_state.npy")), x)
+    full = run(tmp_path / "c", "--full", "--side-steps", "2", "--no-cpu-baseline")
+    assert "batched_8seq" in full and "cfg5_8seq_gqa" in full and "side_error" not in full

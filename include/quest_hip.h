@@ -448,6 +448,19 @@ int quest_apply_rope_in_place(void* q, void* k, uint32_t n, uint32_t past_kv_len
                               uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
                               float rope_scale, float rope_theta, quest_stream_t stream);
 
+/*
+ * RoPE from a frequency table (EXTENSION: the llama3 and yarn scalings of Hugging Face's modeling_rope_utils, whose
+ * frequencies no closed formula in the kernel reproduces bit for bit).  Pair i (features i, i + head_dim/2) at position p
+ * rotates by p * inv_freq[i]; cos and sin are multiplied by attention_factor.  inv_freq: device, head_dim/2 fp32.
+ * states NULL: row i at past_kv_len + i; else row i at states[i].seq_len - 1 (one row per sequence; past_kv_len unused),
+ * so one entry serves the eager, single-state and batched forms.  QUEST_EINVAL for a NULL table or an attention_factor
+ * that is not finite and > 0; head_dim 64 / 128 / 256.  The rope_scale / rope_theta entries (default and linear
+ * scaling) keep their in-kernel formula.
+ */
+int quest_apply_rope_in_place_freqs(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
+                                    uint32_t num_kv_heads, uint32_t head_dim, const float* inv_freq,
+                                    float attention_factor, const quest_step_state_t* states, quest_stream_t stream);
+
 /* rms_norm_forward (bsk_ops.h:29-32, rms_norm.cu:160-212). input/output: [rows][cols], weight [cols]. */
 int quest_rms_norm_forward(const void* input, const void* weight, void* output, uint32_t rows,
                            uint32_t cols, float epsilon, quest_stream_t stream);
@@ -478,7 +491,10 @@ int quest_prefill_with_paged_kv_cache(const void* q, void* o, uint32_t n_q, uint
  *   quest_decode_gemv_residual h[out_dim]  += W . x                           (in place on the residual stream)
  *   quest_decode_mlp_gate_up   act[intermediate] = silu(Wg . n) * (Wu . n),   n = rmsnorm(h; gamma, eps)
  *   quest_decode_qkv_rope      q, k, v = Wq . n, Wk . n, Wv . n with rotate-half RoPE on q and k at position
- *                              state->seq_len - 1 (call after quest_step_state_advance), n = rmsnorm(h; gamma, eps)
+ *                              state->seq_len - 1 (call after quest_step_state_advance), n = rmsnorm(h; gamma, eps);
+ *                              default / linear RoPE: frequency (1 / rope_scale) * rope_theta^(-2i / head_dim)
+ *   quest_decode_qkv_rope_freqs  the same with the frequency table of quest_apply_rope_in_place_freqs (inv_freq:
+ *                              device, head_dim/2 fp32; cos / sin times attention_factor; QUEST_EINVAL like there)
  */
 int quest_decode_norm_gemv(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
                            uint32_t out_dim, quest_stream_t stream);
@@ -490,12 +506,17 @@ int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const voi
                           void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
                           uint32_t head_dim, float rope_scale, float rope_theta, const quest_step_state_t* state,
                           quest_stream_t stream);
+int quest_decode_qkv_rope_freqs(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
+                                void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
+                                uint32_t head_dim, const float* inv_freq, float attention_factor,
+                                const quest_step_state_t* state, quest_stream_t stream);
 /*
  * The same four launches for n_tokens <= 16 decode tokens at once -- one per sequence of a batch (the reference asserts
  * batch size 1; BatchedInferenceController): x / h `[n_tokens][in]`, outputs `[n_tokens][out]` (q / k / v
  * `[n_tokens][heads][head_dim]`), all contiguous; `states` = n_tokens consecutive quest_step_state_t records (the batched
  * step state), token i rotated at states[i].seq_len - 1.  The weights are read once for the whole batch (MFMA row-dots:
- * weights = A operand, tokens = the 16 columns of B); head_dim % 16 == 0 for the q/k/v launch.
+ * weights = A operand, tokens = the 16 columns of B); head_dim % 16 == 0 for the q/k/v launch, which also comes in the
+ * frequency-table form (quest_decode_qkv_rope_batched_freqs, arguments as for quest_decode_qkv_rope_freqs).
  */
 int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
                                    uint32_t out_dim, uint32_t n_tokens, quest_stream_t stream);
@@ -508,6 +529,11 @@ int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, c
                                   const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
                                   uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
                                   const quest_step_state_t* states, uint32_t n_tokens, quest_stream_t stream);
+int quest_decode_qkv_rope_batched_freqs(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+                                        const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
+                                        uint32_t num_kv_heads, uint32_t head_dim, const float* inv_freq,
+                                        float attention_factor, const quest_step_state_t* states, uint32_t n_tokens,
+                                        quest_stream_t stream);
 
 /* Which kernel an n-token launch of this shape takes (tests / tuning; nothing is launched): 1 and info = {k slices per
  * quad of rows, rounds, dynamic LDS bytes, workgroups, 128-wide k steps per row, weight fragments per set} for the persistent

@@ -114,6 +114,37 @@ def apply_rope_in_place(q, k, past_kv_len: int, rope_scale: float, rope_theta: f
           "apply_rope_in_place")
 
 
+def _check_rope_table(inv_freq, head_dim: int) -> None:
+    """The frequency table of the RoPE table form: a contiguous fp32 CUDA tensor of head_dim / 2 elements."""
+    _check_input(inv_freq, "inv_freq")
+    if _CHECKS_ON and inv_freq.dtype != torch.float32:
+        raise RuntimeError("inv_freq must be a float32 tensor")
+    _check_eq(inv_freq.numel(), head_dim // 2, "inv_freq.numel(), head_dim / 2")
+
+
+def apply_rope_in_place_freqs(q, k, inv_freq, attention_factor: float, past_kv_len: int = 0, states=None) -> None:
+    """RoPE from a frequency table (llama3 / yarn; EXTENSION): pair i of a row at position p rotates by
+    ``p * inv_freq[i]``, cos and sin times ``attention_factor``.  q ``[N, Hq, D]``, k ``[N, Hkv, D]`` in place;
+    ``states`` None: row i at ``past_kv_len + i``, else ``states`` ``[N, 8]`` int32 step states and row i at
+    ``states[i].seq_len - 1``."""
+    _check_input(q, "q")
+    _check_input(k, "k")
+    _check_dim(3, q, "q")
+    _check_dim(3, k, "k")
+    _check_eq(q.size(0), k.size(0), "q.size(0), k.size(0)")
+    _check_eq(q.size(2), k.size(2), "q.size(2), k.size(2)")
+    _check_half(q, "apply_rope_in_place")
+    _check_half(k, "apply_rope_in_place")
+    _check_rope_table(inv_freq, q.size(2))
+    if states is not None:
+        _check_input(states, "states")
+        _check_eq(states.numel(), q.size(0) * STEP_STATE_INTS, "states.numel(), n * 8")
+    check(lib.quest_apply_rope_in_place_freqs(q.data_ptr(), k.data_ptr(), q.size(0), int(past_kv_len), q.size(1),
+                                              k.size(1), q.size(2), inv_freq.data_ptr(), float(attention_factor),
+                                              states.data_ptr() if states is not None else None, _stream(q)),
+          "apply_rope_in_place_freqs")
+
+
 def rms_norm_forward(input, weight, output, epsilon: float) -> None:
     """rms_norm.cu:183-212.  input/output ``[1, N, C]``, weight ``[C]``."""
     _check_input(input, "input")
@@ -312,6 +343,28 @@ def decode_qkv_rope(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, ro
                                     float(rope_theta), state.data_ptr(), _stream(h)), "decode_qkv_rope")
 
 
+def decode_qkv_rope_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, inv_freq, attention_factor: float,
+                          state) -> None:
+    """``decode_qkv_rope`` with the RoPE frequency table of ``apply_rope_in_place_freqs`` (llama3 / yarn)."""
+    hidden = wq.size(1)
+    _check_vec(h, hidden, "h")
+    _check_vec(gamma, hidden, "gamma")
+    _check_weight(wq, wq.size(0), hidden, "wq")
+    _check_weight(wk, wk.size(0), hidden, "wk")
+    _check_weight(wv, wk.size(0), hidden, "wv")
+    _check_vec(q, wq.size(0), "q")
+    _check_vec(k, wk.size(0), "k")
+    _check_vec(v, wk.size(0), "v")
+    _check_input(state, "state")
+    _check_eq(wq.size(0) % head_dim, 0, "wq.size(0) % head_dim, 0")
+    _check_rope_table(inv_freq, head_dim)
+    check(lib.quest_decode_qkv_rope_freqs(h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(), wk.data_ptr(),
+                                          wv.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), hidden,
+                                          wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim),
+                                          inv_freq.data_ptr(), float(attention_factor), state.data_ptr(), _stream(h)),
+          "decode_qkv_rope_freqs")
+
+
 # ---- the fused decode-layer launches for n <= 16 tokens (one per sequence of a batch)
 
 MAX_BATCHED_TOKENS = 16
@@ -393,6 +446,31 @@ def decode_qkv_rope_batched(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim:
                                             wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim),
                                             float(rope_scale), float(rope_theta), states.data_ptr(), n, _stream(h)),
           "decode_qkv_rope_batched")
+
+
+def decode_qkv_rope_batched_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, inv_freq,
+                                  attention_factor: float, states) -> None:
+    """``decode_qkv_rope_batched`` with the RoPE frequency table of ``apply_rope_in_place_freqs`` (llama3 / yarn)."""
+    hidden = wq.size(1)
+    n = h.numel() // hidden
+    _check_tokens(n)
+    _check_mat(h, n, hidden, "h")
+    _check_vec(gamma, hidden, "gamma")
+    _check_weight(wq, wq.size(0), hidden, "wq")
+    _check_weight(wk, wk.size(0), hidden, "wk")
+    _check_weight(wv, wk.size(0), hidden, "wv")
+    _check_mat(q, n, wq.size(0), "q")
+    _check_mat(k, n, wk.size(0), "k")
+    _check_mat(v, n, wk.size(0), "v")
+    _check_input(states, "states")
+    _check_eq(states.numel(), n * STEP_STATE_INTS, "states.numel(), n * 8")
+    _check_eq(wq.size(0) % head_dim, 0, "wq.size(0) % head_dim, 0")
+    _check_rope_table(inv_freq, head_dim)
+    check(lib.quest_decode_qkv_rope_batched_freqs(h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(),
+                                                  wk.data_ptr(), wv.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
+                                                  hidden, wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim),
+                                                  inv_freq.data_ptr(), float(attention_factor), states.data_ptr(), n,
+                                                  _stream(h)), "decode_qkv_rope_batched_freqs")
 
 
 # ---- state-driven (graph-replayable) forms: EXTENSIONS, see include/quest_hip.h quest_step_state_t

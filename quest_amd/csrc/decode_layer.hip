@@ -19,6 +19,7 @@
 // the weight loads of the first round are issued BEFORE the prologue so its latency hides under them.  HBM-bound
 // (weights read exactly once): 4.9-5.7 TB/s at Llama-2-7B shapes; no MFMA: M = 1.
 #include <atomic>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 
@@ -46,7 +47,18 @@ struct GemvArgs {
     uint32_t head_dim;
     float rcp_scale, log2_rcp_theta;
     const quest_step_state_t* state;  // position = state->seq_len - 1
+    // frequency table form (llama3 / yarn): NULL = the formula above; else freq_d = inv_freq[d] ([head_dim / 2] fp32) and
+    // cos / sin scaled by attn_factor
+    const float* inv_freq;
+    float attn_factor;
 };
+
+// (cos, sin) of RoPE pair d at position pos: the formula, or the frequency table (p.inv_freq: uniform)
+__device__ __forceinline__ void rope_cos_sin(const GemvArgs& p, uint32_t d, float pos, float& cs, float& sn) {
+    const float freq = p.inv_freq ? p.inv_freq[d] : p.rcp_scale * exp2f(p.log2_rcp_theta * (float)(2 * d) / (float)p.head_dim);
+    sincosf(pos * freq, &sn, &cs);
+    if (p.inv_freq) sn *= p.attn_factor, cs *= p.attn_factor;
+}
 
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
 
@@ -217,10 +229,8 @@ __global__ __launch_bounds__(kGvWaves* kWave, kGvWaves / 2) void gemv_kernel(Gem
         for (int r = 0; r < kGvRows; r += 2) {
             if (!live[r]) continue;
             if (mat[r] < 2) {  // q / k: (acc[r], acc[r+1]) = features (d, d + D/2) of one head
-                const uint32_t d = row[r] % p.head_dim;  // < D/2
-                const float freq = p.rcp_scale * exp2f(p.log2_rcp_theta * (float)(2 * d) / (float)p.head_dim);
                 float s, c;
-                sincosf(pos * freq, &s, &c);
+                rope_cos_sin(p, row[r] % p.head_dim, pos, c, s);  // row[r] % head_dim < D/2
                 p.out[mat[r]][row[r]] = (half_t)(acc[r] * c - acc[r + 1] * s);
                 p.out[mat[r]][row[r + 1]] = (half_t)(acc[r + 1] * c + acc[r] * s);
             } else {
@@ -484,10 +494,8 @@ __global__ __launch_bounds__(NW* kWave, 2) void skinny_kernel(SkinnyArgs a) {  /
         half_t* o = p.out[mat[0]] + (size_t)token * a.out_stride[mat[0]];
         if (mat[0] < 2) {
             const float pos = (float)(p.state[(size_t)token * a.state_stride].seq_len - 1);
-            const uint32_t d = row[0] % p.head_dim;
-            const float freq = p.rcp_scale * exp2f(p.log2_rcp_theta * (float)(2 * d) / (float)p.head_dim);
             float sn, cs;
-            sincosf(pos * freq, &sn, &cs);
+            rope_cos_sin(p, row[0] % p.head_dim, pos, cs, sn);
             o[row[0]] = (half_t)(v0 * cs - v1 * sn);
             o[row[1]] = (half_t)(v1 * cs + v0 * sn);
         } else {
@@ -646,9 +654,8 @@ __global__ __launch_bounds__(kPsWaves* kWave, 4) void persist_kernel(SkinnyArgs 
         for (uint32_t e = tid; e < a.n_tokens * half_d; e += kPsWaves * kWave) {
             const uint32_t t = e / half_d, d = e % half_d;
             const float pos = (float)(p.state[(size_t)t * a.state_stride].seq_len - 1);
-            const float freq = p.rcp_scale * exp2f(p.log2_rcp_theta * (float)(2 * d) / (float)p.head_dim);
             float sn, cs;
-            sincosf(pos * freq, &sn, &cs);
+            rope_cos_sin(p, d, pos, cs, sn);
             s_rope[t * kRopeMaxHalfD + d] = make_float2(cs, sn);
         }
     }
@@ -912,20 +919,44 @@ extern "C" int quest_decode_mlp_gate_up(const void* h, const void* gamma, float 
     return launch_gemv<kGvSiluMul>(p, 2 * intermediate, (hipStream_t)stream);
 }
 
-extern "C" int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
-                                     const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
-                                     uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
-                                     const quest_step_state_t* state, quest_stream_t stream) {
+static int qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
+                    void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
+                    float rcp_scale, float log2_rcp_theta, const float* inv_freq, float attn_factor,
+                    const quest_step_state_t* state, quest_stream_t stream) {
     if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v || !state) return QUEST_EINVAL;
-    if (hidden == 0 || num_qo_heads == 0 || num_kv_heads == 0 || rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
+    if (hidden == 0 || num_qo_heads == 0 || num_kv_heads == 0) return QUEST_EINVAL;
     if (hidden % 8 != 0 || head_dim % 4 != 0) return QUEST_EUNSUPPORTED;  // a wave's 4 row-dots = two rotation pairs of one head
     GemvArgs p{};
     p.x = (const half_t*)h, p.gamma = (const half_t*)gamma, p.eps = eps, p.in_dim = hidden;
     p.w[0] = (const half_t*)wq, p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
     p.rows[0] = num_qo_heads * head_dim, p.rows[1] = p.rows[2] = num_kv_heads * head_dim;
     p.out[0] = (half_t*)q, p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
-    p.head_dim = head_dim, p.rcp_scale = 1.0f / rope_scale, p.log2_rcp_theta = -log2f(rope_theta), p.state = state;
+    p.head_dim = head_dim, p.rcp_scale = rcp_scale, p.log2_rcp_theta = log2_rcp_theta, p.state = state;
+    p.inv_freq = inv_freq, p.attn_factor = attn_factor;
     return launch_gemv<kGvQkvRope>(p, p.rows[0] + p.rows[1] + p.rows[2], (hipStream_t)stream);
+}
+
+static bool bad_rope_table(const float* inv_freq, float attention_factor) {
+    return !inv_freq || !(attention_factor > 0.f) || !std::isfinite(attention_factor);
+}
+
+extern "C" int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+                                     const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
+                                     uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
+                                     const quest_step_state_t* state, quest_stream_t stream) {
+    if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
+    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, 1.0f / rope_scale,
+                    -log2f(rope_theta), nullptr, 1.0f, state, stream);
+}
+
+extern "C" int quest_decode_qkv_rope_freqs(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+                                           const void* wv, void* q, void* k, void* v, uint32_t hidden,
+                                           uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
+                                           const float* inv_freq, float attention_factor,
+                                           const quest_step_state_t* state, quest_stream_t stream) {
+    if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
+    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, 1.0f, 0.f, inv_freq,
+                    attention_factor, state, stream);
 }
 
 // ---- the same for n_tokens <= 16 decode tokens (x: [n_tokens][in_dim], outputs [n_tokens][out_dim], contiguous)
@@ -967,13 +998,12 @@ extern "C" int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma
     return launch_batched<kGvSiluMul>(a, 2 * intermediate, (hipStream_t)stream);
 }
 
-extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
-                                             const void* wv, void* q, void* k, void* v, uint32_t hidden,
-                                             uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
-                                             float rope_scale, float rope_theta, const quest_step_state_t* states,
-                                             uint32_t n_tokens, quest_stream_t stream) {
+static int qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
+                            void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
+                            uint32_t head_dim, float rcp_scale, float log2_rcp_theta, const float* inv_freq,
+                            float attn_factor, const quest_step_state_t* states, uint32_t n_tokens, quest_stream_t stream) {
     if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v || !states) return QUEST_EINVAL;
-    if (hidden == 0 || num_qo_heads == 0 || num_kv_heads == 0 || rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
+    if (hidden == 0 || num_qo_heads == 0 || num_kv_heads == 0) return QUEST_EINVAL;
     if (head_dim % 16 != 0) return QUEST_EUNSUPPORTED;  // a 16-row block = 8 rotation pairs of ONE head of ONE matrix
     SkinnyArgs a{};
     GemvArgs& p = a.g;
@@ -981,11 +1011,33 @@ extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, f
     p.w[0] = (const half_t*)wq, p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
     p.rows[0] = num_qo_heads * head_dim, p.rows[1] = p.rows[2] = num_kv_heads * head_dim;
     p.out[0] = (half_t*)q, p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
-    p.head_dim = head_dim, p.rcp_scale = 1.0f / rope_scale, p.log2_rcp_theta = -log2f(rope_theta), p.state = states;
+    p.head_dim = head_dim, p.rcp_scale = rcp_scale, p.log2_rcp_theta = log2_rcp_theta, p.state = states;
+    p.inv_freq = inv_freq, p.attn_factor = attn_factor;
     a.n_tokens = n_tokens, a.x_stride = hidden;
     a.out_stride[0] = p.rows[0], a.out_stride[1] = p.rows[1], a.out_stride[2] = p.rows[2];
     a.state_stride = 1;
     return launch_batched<kGvQkvRope>(a, p.rows[0] + p.rows[1] + p.rows[2], (hipStream_t)stream);
+}
+
+extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+                                             const void* wv, void* q, void* k, void* v, uint32_t hidden,
+                                             uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
+                                             float rope_scale, float rope_theta, const quest_step_state_t* states,
+                                             uint32_t n_tokens, quest_stream_t stream) {
+    if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
+    return qkv_rope_batched(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
+                            1.0f / rope_scale, -log2f(rope_theta), nullptr, 1.0f, states, n_tokens, stream);
+}
+
+extern "C" int quest_decode_qkv_rope_batched_freqs(const void* h, const void* gamma, float eps, const void* wq,
+                                                   const void* wk, const void* wv, void* q, void* k, void* v,
+                                                   uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
+                                                   uint32_t head_dim, const float* inv_freq, float attention_factor,
+                                                   const quest_step_state_t* states, uint32_t n_tokens,
+                                                   quest_stream_t stream) {
+    if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
+    return qkv_rope_batched(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, 1.0f, 0.f,
+                            inv_freq, attention_factor, states, n_tokens, stream);
 }
 
 // Which kernel an n-token launch of this shape takes (tests / tuning; no launch): returns 1 and fills

@@ -4,8 +4,11 @@
 // Reference behaviour restated (not translated):
 //   rope     QKApplyRotaryInPlaceKernel   kernels/include/decode/decode_page.cuh:644-692
 //            (rotate-half, freq_i = (1/scale) * theta^(-2*(i mod D/2)/D), position = past_len + row)
+//            table form (llama3 / yarn scaling): freq_i = inv_freq[i mod D/2], cos and sin times attention_factor
 //   rmsnorm  rmsnorm_twoPassAlgo_e8       quest/ops/csrc/rms_norm.cu:82-158
 // Both are elementwise / one-row reductions: HBM-bound, 16 B per lane accesses.
+#include <cmath>
+
 #include "quest_common.cuh"
 
 namespace quest {
@@ -13,8 +16,10 @@ namespace quest {
 template <int D>
 __global__ __launch_bounds__(256) void rope_kernel(half_t* __restrict__ q, half_t* __restrict__ k, uint32_t n,
                                                    uint32_t past_len, uint32_t hq, uint32_t hk, float rcp_scale,
-                                                   float log2_rcp_theta, const quest_step_state_t* state) {
+                                                   float log2_rcp_theta, const float* __restrict__ inv_freq, float attn,
+                                                   const quest_step_state_t* state) {
     // state-driven: row i is the decode token of sequence i (one row for a single sequence)
+    // inv_freq (uniform): NULL = the formula, else the [D/2] frequency table with cos / sin scaled by attn
     constexpr int LPR = D / kVec;
     constexpr int RPB = 256 / LPR;  // vectors per block
     const uint32_t vec = blockIdx.x * RPB + threadIdx.x / LPR;
@@ -32,9 +37,11 @@ __global__ __launch_bounds__(256) void rope_kernel(half_t* __restrict__ q, half_
         const int d = col * kVec + i;
         // partner element d +- D/2 lives in lane col +- LPR/2, same i
         const float other = __shfl_xor(self[i], LPR / 2, kWave);
-        const float freq = rcp_scale * exp2f(log2_rcp_theta * (float)(2 * (d % (D / 2))) / (float)D);
+        const float freq = inv_freq ? inv_freq[d % (D / 2)]
+                                    : rcp_scale * exp2f(log2_rcp_theta * (float)(2 * (d % (D / 2))) / (float)D);
         float s, c;
         sincosf(pos * freq, &s, &c);
+        if (inv_freq) s *= attn, c *= attn;
         out[i] = self[i] * c + (d < D / 2 ? -other : other) * s;
     }
     st8(x, __builtin_convertvector(out, half8));
@@ -76,14 +83,11 @@ __global__ __launch_bounds__(1024) void rms_norm_kernel(const half_t* __restrict
 
 using namespace quest;
 
-static int rope_entry(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                      uint32_t head_dim, float rope_scale, float rope_theta, const quest_step_state_t* state,
-                      quest_stream_t stream) {
+static int rope_launch(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads, uint32_t num_kv_heads,
+                       uint32_t head_dim, float rcp_scale, float log2_rcp_theta, const float* inv_freq, float attn,
+                       const quest_step_state_t* state, quest_stream_t stream) {
     if (!q || !k || num_qo_heads == 0 || num_kv_heads == 0) return QUEST_EINVAL;
-    if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
     if (n == 0) return 0;
-    const float rcp_scale = 1.0f / rope_scale;
-    const float log2_rcp_theta = -log2f(rope_theta);
     const uint32_t vecs = n * (num_qo_heads + num_kv_heads);
     hipStream_t s = (hipStream_t)stream;
 #define QUEST_ROPE_CASE(DD)                                                                                       \
@@ -91,7 +95,7 @@ static int rope_entry(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32
         const uint32_t rpb = 256 / (DD / kVec);                                                                   \
         hipLaunchKernelGGL((rope_kernel<DD>), dim3((vecs + rpb - 1) / rpb), dim3(256), 0, s, (half_t*)q,          \
                            (half_t*)k, n, past_kv_len, num_qo_heads, num_kv_heads, rcp_scale, log2_rcp_theta,    \
-                           state);                                                                               \
+                           inv_freq, attn, state);                                                               \
         break;                                                                                                    \
     }
     switch (head_dim) {
@@ -103,6 +107,14 @@ static int rope_entry(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32
 #undef QUEST_ROPE_CASE
     QUEST_LAUNCH_CHECK();
     return 0;
+}
+
+static int rope_entry(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads, uint32_t num_kv_heads,
+                      uint32_t head_dim, float rope_scale, float rope_theta, const quest_step_state_t* state,
+                      quest_stream_t stream) {
+    if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
+    return rope_launch(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, 1.0f / rope_scale, -log2f(rope_theta),
+                       nullptr, 1.0f, state, stream);
 }
 
 extern "C" int quest_apply_rope_in_place(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
@@ -124,6 +136,15 @@ extern "C" int quest_apply_rope_in_place_batched(void* q, void* k, uint32_t num_
                                                  quest_stream_t stream) {
     if (!state || batch.n_seqs == 0) return QUEST_EINVAL;
     return rope_entry(q, k, batch.n_seqs, 0, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta, state, stream);
+}
+
+extern "C" int quest_apply_rope_in_place_freqs(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
+                                               uint32_t num_kv_heads, uint32_t head_dim, const float* inv_freq,
+                                               float attention_factor, const quest_step_state_t* states,
+                                               quest_stream_t stream) {
+    if (!inv_freq || !(attention_factor > 0.f) || !std::isfinite(attention_factor)) return QUEST_EINVAL;
+    return rope_launch(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, 1.0f, 0.f, inv_freq, attention_factor,
+                       states, stream);
 }
 
 extern "C" int quest_rms_norm_forward(const void* input, const void* weight, void* output, uint32_t rows, uint32_t cols,

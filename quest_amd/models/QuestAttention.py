@@ -19,6 +19,7 @@ import torch
 from torch import nn
 
 from .. import utils as qutils
+from . import rope as qrope
 
 
 class QuestAttention(nn.Module):
@@ -40,16 +41,23 @@ class QuestAttention(nn.Module):
         self.k_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=False)
         self.v_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=False)
         self.o_proj = nn.Linear(self.num_heads * self.head_dim, self.hidden_size, bias=False)
-        # rope: default theta 1e4; only linear position interpolation is supported, as in the
-        # reference kernel path (QuestAttention.py:40-51)
+        # rope: default theta 1e4.  Default and linear position interpolation run the kernels' formula, as in the
+        # reference kernel path (QuestAttention.py:40-51); llama3 and yarn scaling the kernels' frequency table
+        # (models/rope.py), held in `rope_freqs` = (device inv_freq, attention_factor) -- NOT a buffer: it must survive
+        # the meta-device construction of from_pretrained, stay out of the state_dict and stay fp32 under .half()
         scaling = getattr(config, "rope_scaling", None)
-        if scaling is None:
-            self.rope_scale = 1.0
-        elif scaling.get("type", scaling.get("rope_type")) == "linear":
-            self.rope_scale = float(scaling["factor"])
-        else:
-            raise ValueError(f"Unknown RoPE scaling type {scaling}")
+        kind = qrope.rope_type(scaling)
+        self.rope_scale = float(scaling["factor"]) if kind == "linear" else 1.0
         self.rope_theta = float(getattr(config, "rope_theta", 1e4))
+        self.rope_table = kind in qrope.TABLE_TYPES
+        self.rope_freqs = None  # set by LlamaForCausalLM.quest_init* (one table for all layers), else on first use
+
+    def rotary(self, device):
+        """The ``rope_freqs`` argument of the ``quest_amd.utils`` launches: None (formula) or the frequency table on
+        ``device``, materialised on first use."""
+        if self.rope_table and (self.rope_freqs is None or self.rope_freqs[0].device != device):
+            self.rope_freqs = qrope.device_rope_parameters(self.config, device)
+        return self.rope_freqs
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.LongTensor] = None, past_key_value: Optional[Tuple[torch.Tensor]] = None,
@@ -69,7 +77,7 @@ class QuestAttention(nn.Module):
 
         nvtx.range_push("RoPE")
         qutils.apply_rope_in_place(q, k, iController.kv_cache.seqlen - q_len, rope_scale=self.rope_scale,
-                                   rope_theta=self.rope_theta)
+                                   rope_theta=self.rope_theta, rope_freqs=self.rotary(q.device))
         nvtx.range_pop()
 
         if q_len > 1:
@@ -131,10 +139,10 @@ class QuestAttention(nn.Module):
         v = self.v_proj(hidden_states).view(1, self.num_key_value_heads, self.head_dim)
         if dense:
             attn = qutils.decode_layer_dense_dyn(q, k, v, iController, self.layer_idx, self.rope_scale, self.rope_theta,
-                                                 apply_rope=True)
+                                                 apply_rope=True, rope_freqs=self.rotary(q.device))
         else:
             attn = qutils.decode_layer_dyn(q, k, v, iController, self.layer_idx, scores, self.rope_scale,
-                                           self.rope_theta, apply_rope=True)
+                                           self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device))
         return self.o_proj(attn.reshape(1, 1, self.hidden_size))
 
 
@@ -150,8 +158,8 @@ class QuestAttention(nn.Module):
         v = self.v_proj(hidden_states).view(n, self.num_key_value_heads, self.head_dim)
         if dense:
             attn = qutils.decode_layer_dense_batched(q, k, v, bController, self.layer_idx, self.rope_scale,
-                                                     self.rope_theta, apply_rope=True)
+                                                     self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device))
         else:
             attn = qutils.decode_layer_batched(q, k, v, bController, self.layer_idx, scores, self.rope_scale,
-                                               self.rope_theta, apply_rope=True)
+                                               self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device))
         return self.o_proj(attn.reshape(n, 1, self.hidden_size))

@@ -18,6 +18,7 @@ import torch
 from torch import nn
 
 from .. import utils as qutils
+from . import rope as rope_mod
 from .QuestAttention import QuestAttention
 
 
@@ -48,6 +49,8 @@ class LlamaConfig:
         scaling = d.get("rope_scaling")
         if scaling is None and rope.get("rope_type", "default") not in ("default", None):
             scaling = {k: v for k, v in rope.items() if k != "rope_theta"}
+        if float(d.get("partial_rotary_factor", rope.get("partial_rotary_factor", 1.0))) != 1.0:
+            raise ValueError("partial rotary embeddings (partial_rotary_factor != 1) are not supported")
         if d.get("attention_bias") or d.get("mlp_bias"):
             raise ValueError("bias terms are not part of the reference's Llama fork")
         head_dim = d.get("head_dim")
@@ -122,9 +125,15 @@ class LlamaDecoderLayer(nn.Module):
         from .. import _kernels
 
         a, m = self.self_attn, self.mlp
-        _kernels.decode_qkv_rope(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon, a.q_proj.weight,
-                                 a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v, a.head_dim, a.rope_scale,
-                                 a.rope_theta, iController.step_state)
+        freqs = a.rotary(h.device)
+        if freqs is None:
+            _kernels.decode_qkv_rope(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon, a.q_proj.weight,
+                                     a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v, a.head_dim, a.rope_scale,
+                                     a.rope_theta, iController.step_state)
+        else:
+            _kernels.decode_qkv_rope_freqs(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon,
+                                           a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v, a.head_dim,
+                                           freqs[0], freqs[1], iController.step_state)
         if dense:
             attn = qutils.decode_layer_dense_dyn(ws.q, ws.k, ws.v, iController, a.layer_idx)
         else:
@@ -143,9 +152,15 @@ class LlamaDecoderLayer(nn.Module):
         from .. import _kernels
 
         a, m = self.self_attn, self.mlp
-        _kernels.decode_qkv_rope_batched(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon,
-                                         a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v, a.head_dim,
-                                         a.rope_scale, a.rope_theta, bController.step_states)
+        freqs = a.rotary(h.device)
+        if freqs is None:
+            _kernels.decode_qkv_rope_batched(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon,
+                                             a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v,
+                                             a.head_dim, a.rope_scale, a.rope_theta, bController.step_states)
+        else:
+            _kernels.decode_qkv_rope_batched_freqs(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon,
+                                                   a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v,
+                                                   a.head_dim, freqs[0], freqs[1], bController.step_states)
         if dense:
             attn = qutils.decode_layer_dense_batched(ws.q, ws.k, ws.v, bController, a.layer_idx, out=ws.attn)
         else:
@@ -377,8 +392,16 @@ class LlamaForCausalLM(nn.Module):
             cfg.num_hidden_layers, cfg.num_attention_heads, cfg.hidden_size // cfg.num_attention_heads, page_size,
             self.model._quest_page_budget, max_seq_len, dtype, device, num_kv_heads=cfg.num_key_value_heads,
             layout=qutils.TensorLayout.parse(kv_layout))
+        self._share_rope_table(device)
         print(f"Quest allocates KV-Cache of {max_seq_len} tokens; token_budget {token_budget} = "
               f"{self.model._quest_page_budget} pages of {page_size}")
+
+    def _share_rope_table(self, device) -> None:
+        """llama3 / yarn configs: ONE fp32 frequency table on ``device`` for every layer (kept referenced by the layers
+        for as long as a captured graph may use its address)."""
+        freqs = rope_mod.device_rope_parameters(self.config, device)
+        for layer in self.model.layers:
+            layer.self_attn.rope_freqs = freqs
 
     def quest_clear(self) -> None:
         """llama.py:554-560: release the pages for the next request."""
@@ -475,6 +498,7 @@ class LlamaForCausalLM(nn.Module):
             n_seqs, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.hidden_size // cfg.num_attention_heads,
             page_size, self.model._quest_page_budget, max_seq_len, dtype, device,
             num_kv_heads=cfg.num_key_value_heads, layout=qutils.TensorLayout.parse(kv_layout))
+        self._share_rope_table(device)
 
     def prefill_sequence(self, seq: int, input_ids: torch.Tensor) -> torch.Tensor:
         """Run the prompt of sequence ``seq`` (``[1, L]``) through the ordinary single-sequence path over the

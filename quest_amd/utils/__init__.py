@@ -6,7 +6,7 @@ All tensors are NHD/HND per ``iController.layout``; q/k/v projections are ``[tok
 from __future__ import annotations
 
 import os
-from typing import Optional
+from typing import Optional, Tuple
 
 import torch
 
@@ -54,8 +54,13 @@ def _rope_defaults(rope_scale, rope_theta):
 
 
 def apply_rope_in_place(q: torch.Tensor, k: torch.Tensor, past_kv_len: int, rope_scale: Optional[float] = None,
-                        rope_theta: Optional[float] = None) -> None:
-    """Rotate q ``[N, Hq, D]`` and k ``[N, Hkv, D]`` in place; row i sits at position ``past_kv_len + i``."""
+                        rope_theta: Optional[float] = None, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> None:
+    """Rotate q ``[N, Hq, D]`` and k ``[N, Hkv, D]`` in place; row i sits at position ``past_kv_len + i``.
+    ``rope_freqs``: ``(inv_freq, attention_factor)`` of a llama3 / yarn config (``quest_amd.models.rope``; inv_freq a
+    ``[D/2]`` fp32 device tensor) -- the kernels' frequency-table form, which ignores rope_scale / rope_theta."""
+    if rope_freqs is not None:
+        _kernels.apply_rope_in_place_freqs(q, k, rope_freqs[0], rope_freqs[1], past_kv_len=past_kv_len)
+        return
     scale, theta = _rope_defaults(rope_scale, rope_theta)
     _kernels.apply_rope_in_place(q, k, past_kv_len, scale, theta)
 
@@ -201,6 +206,22 @@ def _need_state(controller) -> None:
                            "prefill (clean_states() / quest_clear() drop it)")
 
 
+def _rope_dyn(q, k, rope_scale, rope_theta, rope_freqs, state) -> None:
+    if rope_freqs is not None:
+        _kernels.apply_rope_in_place_freqs(q, k, rope_freqs[0], rope_freqs[1], states=state)
+        return
+    scale, theta = _rope_defaults(rope_scale, rope_theta)
+    _kernels.apply_rope_in_place_dyn(q, k, scale, theta, state)
+
+
+def _rope_batched(q, k, rope_scale, rope_theta, rope_freqs, states) -> None:
+    if rope_freqs is not None:
+        _kernels.apply_rope_in_place_freqs(q, k, rope_freqs[0], rope_freqs[1], states=states)
+        return
+    scale, theta = _rope_defaults(rope_scale, rope_theta)
+    _kernels.apply_rope_in_place_batched(q, k, scale, theta, states)
+
+
 def step_advance_dyn(iController: InferenceController) -> None:
     _need_state(iController)
     _kernels.step_state_advance(iController.step_state, iController.kv_table_full, iController.meta_table_full,
@@ -210,21 +231,22 @@ def step_advance_dyn(iController: InferenceController) -> None:
 def decode_layer_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iController: InferenceController,
                      layer_idx: int, scores: torch.Tensor, rope_scale: Optional[float] = None,
                      rope_theta: Optional[float] = None, apply_rope: bool = False,
-                     tiles: Optional[bool] = None, advance_after: bool = False) -> torch.Tensor:
+                     tiles: Optional[bool] = None, advance_after: bool = False,
+                     rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
     """One layer of a decode token in the sparse regime (pages > budget), every length read from the
     device-resident state: [RoPE] -> append+estimate -> top-k+attention (+merge).  ``scores`` is a
     caller-owned ``[Hq, >= max_pages]`` fp16 scratch (``score_scratch``).  ``tiles``: None = the tiles launches for pools
     of at least ``iController.tiles_min_pages`` pages (where the scratch has room and the plan allows), True / False force.
     ``advance_after``: the LAST layer of a step -- the next token's reservation (``step_advance_dyn``) rides in this layer's
     merge launch instead of heading the next step as a launch of its own (the first token is reserved by one
-    ``step_advance_dyn`` before the first step; the host mirror ``prepare_metadata(1)`` follows every step as before)."""
+    ``step_advance_dyn`` before the first step; the host mirror ``prepare_metadata(1)`` follows every step as before).
+    ``rope_freqs``: the frequency-table RoPE of ``apply_rope_in_place`` (llama3 / yarn configs)."""
     ctl = iController
     _need_state(ctl)
     if advance_after:
         ctl._decode_handler.arm_step_advance(ctl.step_state, ctl.kv_table_full, ctl.meta_table_full, ctl.page_size)
     if apply_rope:
-        scale, theta = _rope_defaults(rope_scale, rope_theta)
-        _kernels.apply_rope_in_place_dyn(q, k, scale, theta, ctl.step_state)
+        _rope_dyn(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_state)
     max_n = ctl.max_pages - 1
     # long rows: the estimate hands the rows' tile maxima (per 8 pages the largest score) to the attention launch, which
     # then selects in two short passes (csrc/decode_device.cuh sparse_decode_tiles_body); same selection, same outputs
@@ -247,7 +269,8 @@ def decode_layer_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iControl
 
 def decode_layer_dense_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iController: InferenceController,
                            layer_idx: int, rope_scale: Optional[float] = None, rope_theta: Optional[float] = None,
-                           apply_rope: bool = False, fuse_append: bool = True, advance_after: bool = False) -> torch.Tensor:
+                           apply_rope: bool = False, fuse_append: bool = True, advance_after: bool = False,
+                           rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
     """One FULL-KV layer of a decode token (``advance_after``: see ``decode_layer_dyn``), every length read from the device-resident state:
     [RoPE] -> append + attention over all pages in ONE launch (group-shared kernel; the workgroup that attends the
     current page takes the new token from k / v, writes it to the pool and folds it into the metadata) (+merge).  Shapes
@@ -255,8 +278,7 @@ def decode_layer_dense_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iC
     ctl = iController
     _need_state(ctl)
     if apply_rope:
-        scale, theta = _rope_defaults(rope_scale, rope_theta)
-        _kernels.apply_rope_in_place_dyn(q, k, scale, theta, ctl.step_state)
+        _rope_dyn(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_state)
     o = torch.empty_like(q)
     kvb, mb = ctl.kv_cache.buf_layer(layer_idx), ctl.metadata_cache.buf_layer(layer_idx)
     if advance_after:
@@ -282,7 +304,7 @@ def decode_layer_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bCon
                          layer_idx: int, scores: torch.Tensor, rope_scale: Optional[float] = None,
                          rope_theta: Optional[float] = None, apply_rope: bool = False,
                          out: Optional[torch.Tensor] = None, one_launch: Optional[bool] = None,
-                         write_scores: bool = False) -> torch.Tensor:
+                         write_scores: bool = False, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
     """``decode_layer_dyn`` for every sequence at once; ``scores`` is ``[n_seqs, Hq, >= max_pages]`` fp16.
 
     ``one_launch``: None (default) = the controller's choice (``BatchedInferenceController.one_launch_layers``): ONE
@@ -300,8 +322,7 @@ def decode_layer_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bCon
     b = bController
     _need_state(b)
     if apply_rope:
-        scale, theta = _rope_defaults(rope_scale, rope_theta)
-        _kernels.apply_rope_in_place_batched(q, k, scale, theta, b.step_states)
+        _rope_batched(q, k, rope_scale, rope_theta, rope_freqs, b.step_states)
     max_n = b.max_pages - 1
     if (b.one_launch_layers if one_launch is None else one_launch):
         o = torch.empty_like(q) if out is None else out
@@ -369,13 +390,12 @@ def decode_layer_dense_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor
                                bController: BatchedInferenceController, layer_idx: int,
                                rope_scale: Optional[float] = None, rope_theta: Optional[float] = None,
                                apply_rope: bool = False, out: Optional[torch.Tensor] = None,
-                               fuse_append: bool = True) -> torch.Tensor:
+                               fuse_append: bool = True, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
     """``decode_layer_dense_dyn`` for every sequence at once (needs ``begin_graph_decode(dense_layers=True)``)."""
     b = bController
     _need_state(b)
     if apply_rope:
-        scale, theta = _rope_defaults(rope_scale, rope_theta)
-        _kernels.apply_rope_in_place_batched(q, k, scale, theta, b.step_states)
+        _rope_batched(q, k, rope_scale, rope_theta, rope_freqs, b.step_states)
     o = torch.empty_like(q) if out is None else out
     kvb, mb = b.kv_layer(layer_idx), b.metadata_layer(layer_idx)
     if not (fuse_append and b._dense_handler.append_forward_shared_batched(k, v, mb, b.meta_tables, q, o, kvb, b.kv_tables,

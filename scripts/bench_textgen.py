@@ -121,6 +121,9 @@ def main():
                     help="fill the cache the way the reference's harness does (scripts/bench_textgen.py:77-84): ONE model "
                          "forward over --ctx random hidden states -- projections, RoPE, append with page metadata, the MFMA "
                          "prefill attention kernel, MLP in every layer -- and report its latency (time to first token)")
+    ap.add_argument("--rope", choices=["default", "llama3"], default="default",
+                    help="RoPE of the random-weight model: default (theta 1e4, the in-kernel formula) or Llama-3.1's "
+                         "llama3 scaling (theta 5e5, factor 8: the kernels' frequency-table form)")
     a = ap.parse_args()
     from quest_amd.models.llama import LlamaConfig, LlamaForCausalLM
     import quest_amd.utils as qu
@@ -129,6 +132,10 @@ def main():
     torch.manual_seed(0)
     cfg = LlamaConfig(vocab_size=a.vocab, hidden_size=a.hidden, intermediate_size=a.inter, num_hidden_layers=a.layers,
                       num_attention_heads=a.heads, num_key_value_heads=a.kv_heads, max_position_embeddings=a.ctx + 1024)
+    if a.rope == "llama3":
+        cfg.rope_scaling = {"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0, "high_freq_factor": 4.0,
+                            "original_max_position_embeddings": 8192}
+        cfg.rope_theta = 500000.0
     ckpt_info = None
     if a.make_checkpoint:
         import time
@@ -228,7 +235,7 @@ def main():
         torch.cuda.empty_cache()
     out = {"bench": "e2e decode latency, random-weight Llama", "ctx": a.ctx, "token_budget": a.token_budget,
            "page_budget_pages": a.token_budget // 16, "layers": a.layers, "hidden": a.hidden, "heads": a.heads,
-           "kv_heads": a.kv_heads, "dense_first_layers": 2, "kv_layout": a.layout,
+           "kv_heads": a.kv_heads, "dense_first_layers": 2, "kv_layout": a.layout, "rope": a.rope,
            "ms_per_token_quest": results["quest"], "ms_per_token_full_kv": results["dense"],
            "speedup": results["dense"] / results["quest"],
            "reference_published": "RTX 6000 Ada, ctx 32768 FP16: 36.8 ms -> 21.2 ms @ budget 2048 (1.74x)"}

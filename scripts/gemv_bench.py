@@ -2,7 +2,9 @@
 """Per-launch time of the fused decoder-layer GEMV launches at Llama-2-7B shapes (rotating weight sets past the Infinity
 Cache, hipGraph + HIP events).  QUEST_GEMV_CFG="RW,U" forces a workgroup shape.   python scripts/gemv_bench.py
 With --tokens N (2..16): the N-token launches (csrc/decode_layer.hip skinny_kernel; QUEST_SKINNY_CFG="NW,U") next to
-torch.nn.functional.linear on the same [N, in] inputs (hipBLASLt)."""
+torch.nn.functional.linear on the same [N, in] inputs (hipBLASLt).
+With --rope-ab: the q/k/v+RoPE launch at Llama-3.1-8B shapes (hidden 4096, 32 / 8 heads, head_dim 128), batch 1 and 8
+tokens, RoPE formula (rope_scale / rope_theta) vs the llama3 frequency table, alternating A B A B."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -49,3 +51,35 @@ if "--tokens" in sys.argv:
     rows.append(("linear down    86 MiB", graph_time(lambda i: lin(XI, wd[i]), NSET, 20), 86))
     rows.append(("linear gate    86 MiB", graph_time(lambda i: lin(X, wg[i]), NSET, 20), 86))
     print(f"{n} tokens torch ", " | ".join(f"{nm}: {t:6.2f} us {m * 1.048576 / t:5.2f} TB/s" for nm, t, m in rows))
+
+if "--rope-ab" in sys.argv:
+    from quest_amd.models import rope as qrope
+    from types import SimpleNamespace
+    cfg31 = SimpleNamespace(hidden_size=4096, num_attention_heads=32, max_position_embeddings=131072, rope_theta=500000.0,
+                            rope_scaling={"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0,
+                                          "high_freq_factor": 4.0, "original_max_position_embeddings": 8192})
+    inv_freq, factor = qrope.device_rope_parameters(cfg31, dev)
+    wk8, wv8 = w(1024, H), w(1024, H)
+    k8 = torch.empty(1, 8, 128, device=dev, dtype=torch.float16); v8 = torch.empty_like(k8)
+    X8 = torch.randn(8, H, generator=g, device=dev, dtype=torch.float16)
+    Q8 = torch.empty(8, 32, 128, device=dev, dtype=torch.float16); K8 = torch.empty(8, 8, 128, device=dev, dtype=torch.float16)
+    V8 = torch.empty_like(K8)
+    ST8 = torch.tensor([[100000 + 17 * i, 1, 1, 0, 1, 1, 0, 0] for i in range(8)], dtype=torch.int32, device=dev)
+    st1 = torch.tensor([100000, 1, 1, 0, 1, 1, 0, 0], dtype=torch.int32, device=dev)
+    launches = {
+        ("batch 1", "formula"): lambda i: _kernels.decode_qkv_rope(x, gamma, 1e-5, wq[i], wk8[i], wv8[i], q, k8, v8, 128, 1.0,
+                                                                 500000.0, st1),
+        ("batch 1", "table"): lambda i: _kernels.decode_qkv_rope_freqs(x, gamma, 1e-5, wq[i], wk8[i], wv8[i], q, k8, v8, 128,
+                                                                     inv_freq, factor, st1),
+        ("8 tokens", "formula"): lambda i: _kernels.decode_qkv_rope_batched(X8, gamma, 1e-5, wq[i], wk8[i], wv8[i], Q8, K8, V8,
+                                                                          128, 1.0, 500000.0, ST8),
+        ("8 tokens", "table"): lambda i: _kernels.decode_qkv_rope_batched_freqs(X8, gamma, 1e-5, wq[i], wk8[i], wv8[i], Q8, K8,
+                                                                              V8, 128, inv_freq, factor, ST8),
+    }
+    times = {key: [] for key in launches}
+    for _ in range(4):  # A B A B
+        for key, fn in launches.items():
+            times[key].append(graph_time(fn, NSET, 20))
+    for key, ts in times.items():
+        print(f"qkv+rope Llama-3.1-8B {key[0]:8s} {key[1]:7s}: " + " ".join(f"{t:6.2f}" for t in ts)
+              + f"  us (median {sorted(ts)[len(ts) // 2]:6.2f}, 48 MiB: {48 * 1.048576 / sorted(ts)[len(ts) // 2]:5.2f} TB/s)")

@@ -347,6 +347,31 @@ int quest_decode_forward_fused_topk_batched(quest_decode_handler_t* h, const voi
                                             uint32_t score_stride, uint32_t max_n_scores,
                                             const quest_step_state_t* state, quest_batch_t batch, float* lse,
                                             quest_stream_t stream);
+/*
+ * The tiles pair (quest_append_estimate_tiles_dyn / quest_decode_forward_fused_topk_tiles_dyn above) for n_seqs sequences
+ * in one launch each: the same device code, of which the _tiles_dyn pair is the n_seqs == 1 case.  o / scores are
+ * [n_seqs][num_qo_heads][stride]; every row carries its own tile maxima at tile_max_offset (= max_n rounded up to 8; rows
+ * 16-byte aligned: base 16-byte aligned and stride a multiple of 8 with stride >= tile_max_offset + ceil(max_n / 8)
+ * rounded up to 4).  All sequences share the capacity max_n; sequence i's live row (state[i].n_pages - 1 columns) may be
+ * shorter, down to empty: only the maxima of its live runs of 8 pages are written and read, whatever lies behind them in
+ * the row is never looked at.  Per-sequence budgets (batch.page_budgets), a sequence shorter than its budget (it attends
+ * all of its pages) and quest_decode_set_selection_out work as in the whole-row batched pair.  Selections and outputs are
+ * those of quest_append_estimate_batched + quest_decode_forward_fused_topk_batched under the same plan, bit for bit.
+ * QUEST_EINVAL: tile_max_offset == 0 or not max_n rounded up to 8, a stride without room for the maxima, misaligned
+ * rows, n_seqs == 0, a KV table stride shorter than max_n + 1 or a metadata table that does not cover max_n (n_seqs > 1).
+ * QUEST_ESTATE: no plan, or a plan for fewer sequences.  QUEST_EUNSUPPORTED, before anything is launched: page size other
+ * than 16, more than 256 selected pages, rows beyond 16384 pages, an estimate shape with no tile 8 pages wide -- the
+ * caller then issues the whole-row pair.  quest_decode_last_launch_info reports front-end variant 8 and n_seqs.
+ */
+int quest_append_estimate_tiles_batched(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
+                                        uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
+                                        uint32_t tile_max_offset, quest_paged_kv_t metadata,
+                                        const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream);
+int quest_decode_forward_fused_topk_tiles_batched(quest_decode_handler_t* h, const void* q, void* o,
+                                                  quest_paged_kv_t paged_kv, uint32_t num_qo_heads, const void* scores,
+                                                  uint32_t score_stride, uint32_t max_n_scores, uint32_t tile_max_offset,
+                                                  const quest_step_state_t* state, quest_batch_t batch, float* lse,
+                                                  quest_stream_t stream);
 int quest_append_kv_cache_decode_batched(const void* k, const void* v, quest_paged_kv_t kv, quest_paged_kv_t metadata,
                                          const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream);
 int quest_decode_forward_shared_batched(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,

@@ -594,7 +594,11 @@ def step_state_advance_batched(state, kv_tables, meta_tables, page_size: int) ->
 
 
 def append_estimate_batched(k, v, kv_data, kv_tables, q, o, metadata_data, meta_tables, state, max_n_out: int,
-                            layout: int) -> None:
+                            layout: int, tiles: bool = False) -> bool:
+    """``append_estimate_dyn`` for ``n`` sequences in one launch: k/v ``[n, Hkv, D]``, q ``[n, Hq, D]``, o ``[n, Hq, stride]``.
+    ``tiles``: every row also gets its tile maxima at column ``tile_max_offset(max_n_out)`` (``o.size(2)`` must be at
+    least ``tiles_row_stride(max_n_out)``); returns False (nothing launched) for QUEST_EUNSUPPORTED, as
+    ``append_estimate_dyn`` does -- the caller then issues the whole-row launch (``tiles=False``)."""
     for t, n in ((k, "k"), (v, "v"), (kv_data, "kv_data"), (q, "q"), (o, "o"), (metadata_data, "metadata_data"),
                  (state, "state")):
         _check_input(t, n)
@@ -611,9 +615,19 @@ def append_estimate_batched(k, v, kv_data, kv_tables, q, o, metadata_data, meta_
     _check_half(q, "Estimate_attn_score")
     kv = _paged(kv_data, kv_tables, None, 1, 0, layout)
     meta = _paged(metadata_data, meta_tables, None, 1, 0, layout)
+    if tiles:
+        _check_ge(o.size(2), tiles_row_stride(max_n_out), "o.size(2), tiles_row_stride(max_n_out)")
+        code = lib.quest_append_estimate_tiles_batched(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1),
+                                                       o.size(2), int(max_n_out), tile_max_offset(max_n_out), meta,
+                                                       state.data_ptr(), b, _stream(k))
+        if code == -2:
+            return False
+        check(code, "append_estimate_batched")
+        return True
     check(lib.quest_append_estimate_batched(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1),
                                             o.size(2), int(max_n_out), meta, state.data_ptr(), b, _stream(k)),
           "append_estimate_batched")
+    return True
 
 
 def estimate_attn_score_batched(q, o, metadata_data, meta_tables, state, max_n_out: int, layout: int) -> None:
@@ -913,8 +927,10 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
               "BatchDecodeWithPagedKVCache")
 
     def forward_fused_topk_batched(self, q, o, paged_kv_data, kv_tables, scores, state, max_n_scores: int,
-                                   budgets=None) -> None:
-        """forward_fused_topk_dyn for ``n`` sequences in one launch: q/o ``[n, Hq, D]``, scores ``[n, Hq, stride]``."""
+                                   budgets=None, tiles: bool = False) -> bool:
+        """forward_fused_topk_dyn for ``n`` sequences in one launch: q/o ``[n, Hq, D]``, scores ``[n, Hq, stride]``.
+        ``tiles``: the rows carry their tile maxima (``append_estimate_batched(..., tiles=True)`` wrote them); returns
+        False (nothing launched) where the plan is outside what the tiles launch serves, as ``forward_fused_topk_dyn``."""
         for t, n in ((q, "q"), (o, "o"), (paged_kv_data, "paged_kv_data"), (scores, "scores"), (state, "state")):
             _check_input(t, n)
         b = _batch(state, kv_tables, None, budgets)
@@ -926,10 +942,21 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_ge(scores.size(2), max_n_scores, "scores.size(2), max_n_scores")
         _check_half(q, "BatchDecodeWithPagedKVCache")
         kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
+        if tiles:
+            _check_ge(scores.size(2), tiles_row_stride(max_n_scores), "scores.size(2), tiles_row_stride(max_n_scores)")
+            code = lib.quest_decode_forward_fused_topk_tiles_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
+                                                                     scores.data_ptr(), scores.size(2), int(max_n_scores),
+                                                                     tile_max_offset(max_n_scores), state.data_ptr(), b,
+                                                                     None, _stream(q))
+            if code == -2:
+                return False
+            check(code, "BatchDecodeWithPagedKVCache")
+            return True
         check(lib.quest_decode_forward_fused_topk_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
                                                           scores.data_ptr(), scores.size(2), int(max_n_scores),
                                                           state.data_ptr(), b, None, _stream(q)),
               "BatchDecodeWithPagedKVCache")
+        return True
 
     def layer_fused_batched(self, k, v, metadata_data, meta_tables, q, o, paged_kv_data, kv_tables, state,
                             max_n_scores: int, budgets=None, scores_out=None) -> bool:

@@ -83,6 +83,10 @@ SIGNATURES = {
                                                       c_vp, Batch, c_vp]),
     "quest_decode_forward_fused_topk_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_u32,
                                                                 c_vp, Batch, c_vp, c_vp]),
+    "quest_append_estimate_tiles_batched": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32,
+                                                            PagedKV, c_vp, Batch, c_vp]),
+    "quest_decode_forward_fused_topk_tiles_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_u32,
+                                                                      c_u32, c_vp, Batch, c_vp, c_vp]),
     "quest_decode_layer_fused_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_vp, c_vp, PagedKV, c_u32, c_u32, c_vp,
                                                          Batch, c_vp, c_u32, c_vp, c_vp]),
     "quest_append_kv_cache_decode_batched": (ctypes.c_int, [c_vp, c_vp, PagedKV, PagedKV, c_vp, Batch, c_vp]),

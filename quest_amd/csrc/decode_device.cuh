@@ -700,6 +700,10 @@ __device__ __forceinline__ void sparse_decode_body(DecodeParams p, const uint32_
 //      short-row selection over <= 4 keys per thread with the validity mask -- same threshold, same ties, same slots as the
 //      selection over the whole row (tests/test_gpu_long_rows.py, test_gpu_full_size.py cfg 4).
 // Serves k <= 256 (two threads per candidate tile at 512 threads) and rows up to 16384 columns (4 tile keys per thread).
+// One sequence or a batch (`seq` = blockIdx.z; quest_decode_forward_fused_topk_tiles_batched): every quantity below the loads is
+// the sequence's own -- live row length n, n_tiles, k1 and the budget-clamped n_sel -- while the load addresses depend on the shared
+// capacity only; a tile key beyond the sequence's n_tiles (never written by its estimate) is masked in pass 1, a column beyond n
+// in pass 2.  A sequence with an empty row (one page) or a budget of one page skips both passes and attends its current page.
 constexpr int kTileCols = 8;
 template <int D, int NW>
 __device__ __forceinline__ void sparse_decode_tiles_body(DecodeParams p, const uint32_t chunk, const uint32_t hq,

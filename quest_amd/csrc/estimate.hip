@@ -238,6 +238,23 @@ extern "C" int quest_append_estimate_batched(const void* k, const void* v, quest
     return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, batch, stream);
 }
 
+// The batched twin of quest_append_estimate_tiles_dyn: every row of `o` ([n_seqs][num_qo_heads][o_stride]) carries its own
+// tile maxima at `tile_max_offset`.  The grid is sized for the shared capacity; a shorter sequence writes the maxima of
+// its live runs only, and the attention launch masks the tile keys beyond them.
+extern "C" int quest_append_estimate_tiles_batched(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
+                                                   uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
+                                                   uint32_t tile_max_offset, quest_paged_kv_t metadata,
+                                                   const quest_step_state_t* state, quest_batch_t batch,
+                                                   quest_stream_t stream) {
+    if (tile_max_offset == 0 || tile_max_offset != ((max_n_out + 7u) & ~7u)) return QUEST_EINVAL;
+    // rows 16-byte aligned: what the attention launch's 8-byte score loads and 4-byte tile-key loads are checked against
+    if (((uintptr_t)o & 15u) != 0 || o_stride % 8u != 0) return QUEST_EINVAL;
+    // every sequence's metadata table must cover the entries the grid is sized for
+    if (batch.n_seqs > 1 && (uint64_t)batch.meta_table_stride * metadata.page_size < max_n_out) return QUEST_EINVAL;
+    return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, batch, stream,
+                                 tile_max_offset);
+}
+
 extern "C" int quest_append_estimate_strided(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
                                              uint32_t num_qo_heads, uint32_t n_out, uint32_t o_stride,
                                              quest_paged_kv_t metadata, quest_stream_t stream) {

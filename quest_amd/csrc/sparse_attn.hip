@@ -801,7 +801,7 @@ static int plan_decode(quest_decode_handler_t* h, const void* q, void* o, quest_
         if (!fused || tile_off != ((n_scores + 7u) & ~7u) || ((uintptr_t)scores & 15u) != 0 || p.score_stride % 8u != 0 ||
             p.score_stride < tile_off + ((tiles_cap + 3u) & ~3u))
             return QUEST_EINVAL;
-        if (kv.page_size != 16 || h->n_sel > 256u || tiles_cap > 4u * 512u || batch.n_seqs != 1) return QUEST_EUNSUPPORTED;
+        if (kv.page_size != 16 || h->n_sel > 256u || tiles_cap > 4u * 512u) return QUEST_EUNSUPPORTED;
         p.vec_front = 8;
         p.stage_ids = 0;
         p.ids_lds_offset = 0;
@@ -1081,6 +1081,19 @@ extern "C" int quest_decode_forward_fused_topk_batched(quest_decode_handler_t* h
     if (batch.n_seqs > 1 && batch.kv_table_stride < max_n_scores + 1) return QUEST_EINVAL;
     return decode_entry(h, q, o, kv, num_qo_heads, scores, max_n_scores, nullptr, nullptr, lse, (hipStream_t)stream,
                         score_stride, state, batch);
+}
+
+// The batched twin of quest_decode_forward_fused_topk_tiles_dyn (same body, blockIdx.z = sequence): every row of `scores`
+// carries its tile maxima at `tile_max_offset`; live lengths and budgets per sequence as in the whole-row batched entry.
+extern "C" int quest_decode_forward_fused_topk_tiles_batched(quest_decode_handler_t* h, const void* q, void* o,
+                                                             quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
+                                                             uint32_t score_stride, uint32_t max_n_scores,
+                                                             uint32_t tile_max_offset, const quest_step_state_t* state,
+                                                             quest_batch_t batch, float* lse, quest_stream_t stream) {
+    if (!scores || !state || score_stride < max_n_scores || tile_max_offset == 0) return QUEST_EINVAL;
+    if (batch.n_seqs > 1 && batch.kv_table_stride < max_n_scores + 1) return QUEST_EINVAL;
+    return decode_entry(h, q, o, kv, num_qo_heads, scores, max_n_scores, nullptr, nullptr, lse, (hipStream_t)stream,
+                        score_stride, state, batch, tile_max_offset);
 }
 
 // append + estimate + top-k + sparse attention of one layer for a whole batch in ONE launch (layer_device.cuh).

@@ -187,8 +187,10 @@ def score_scratch(controller) -> torch.Tensor:
     load (second-generation top-k front end, csrc/topk_bitmap.cuh).  Any ``[.., >= max_pages]`` fp16 tensor works;
     other strides take the first-generation front end (rows up to 4096 pages)."""
     stride = (controller.max_pages + 7) // 8 * 8
-    if not isinstance(controller, BatchedInferenceController):
-        # room for the rows' tile maxima behind the scores (long-row launches, ``decode_layer_dyn``)
+    # room for the rows' tile maxima behind the scores (long-row launches, ``decode_layer_dyn``); a batch gets it only
+    # where ``decode_layer_batched`` would take the tiles launches, shorter batched scratches keep their shape
+    if not isinstance(controller, BatchedInferenceController) or \
+            controller.max_pages - 1 >= getattr(controller, "tiles_min_pages", 4097):
         stride = max(stride, _kernels.tiles_row_stride(controller.max_pages - 1))
     shape = (controller.num_heads, stride)
     if isinstance(controller, BatchedInferenceController):
@@ -304,8 +306,14 @@ def decode_layer_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bCon
                          layer_idx: int, scores: torch.Tensor, rope_scale: Optional[float] = None,
                          rope_theta: Optional[float] = None, apply_rope: bool = False,
                          out: Optional[torch.Tensor] = None, one_launch: Optional[bool] = None,
-                         write_scores: bool = False, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
+                         write_scores: bool = False, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None,
+                         tiles: Optional[bool] = None) -> torch.Tensor:
     """``decode_layer_dyn`` for every sequence at once; ``scores`` is ``[n_seqs, Hq, >= max_pages]`` fp16.
+
+    ``tiles`` (two-launch form): None = the tiles launches for pools of at least ``bController.tiles_min_pages`` pages per
+    sequence, where the scratch has room for the tile maxima (``score_scratch`` leaves it from that size up) and the
+    largest budget selects at most 256 pages; True / False force.  Where either tiles launch does not serve the plan or
+    shape the whole-row pair runs instead -- same selections, same outputs.
 
     ``one_launch``: None (default) = the controller's choice (``BatchedInferenceController.one_launch_layers``): ONE
     launch per layer where the plan allows it -- one workgroup per (sequence, head) that appends, scores its head's pages
@@ -334,11 +342,19 @@ def decode_layer_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bCon
         if one_launch:
             raise RuntimeError("the one-launch layer does not serve this plan / shape (needs one workgroup per head, "
                                "page_size 16, head_dim 64 / 128, <= 255 selected pages, rows <= 4096 pages)")
-    _kernels.append_estimate_batched(k, v, b.kv_layer(layer_idx), b.kv_tables, q, scores, b.metadata_layer(layer_idx),
-                                     b.meta_tables, b.step_states, max_n, b.layout)
+    # long rows: tile maxima handed from the estimate to the attention launch, as in decode_layer_dyn
+    tiles = (tiles if tiles is not None else max_n >= getattr(b, "tiles_min_pages", 4097)) and scores.dim() == 3 \
+        and scores.size(2) >= _kernels.tiles_row_stride(max_n) and b.inference_page_budget - 1 <= 256
+    tiles = _kernels.append_estimate_batched(k, v, b.kv_layer(layer_idx), b.kv_tables, q, scores, b.metadata_layer(layer_idx),
+                                             b.meta_tables, b.step_states, max_n, b.layout, tiles=True) if tiles else False
+    if not tiles:
+        _kernels.append_estimate_batched(k, v, b.kv_layer(layer_idx), b.kv_tables, q, scores, b.metadata_layer(layer_idx),
+                                         b.meta_tables, b.step_states, max_n, b.layout)
     o = torch.empty_like(q) if out is None else out
-    b._decode_handler.forward_fused_topk_batched(q, o, b.kv_layer(layer_idx), b.kv_tables, scores, b.step_states, max_n,
-                                                 b.page_budgets)
+    if not (tiles and b._decode_handler.forward_fused_topk_batched(q, o, b.kv_layer(layer_idx), b.kv_tables, scores,
+                                                                   b.step_states, max_n, b.page_budgets, tiles=True)):
+        b._decode_handler.forward_fused_topk_batched(q, o, b.kv_layer(layer_idx), b.kv_tables, scores, b.step_states, max_n,
+                                                     b.page_budgets)
     b.last_layer_launches = 2
     return o
 

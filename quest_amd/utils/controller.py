@@ -257,6 +257,8 @@ class BatchedInferenceController:
         # each stream their kv head's metadata (cfg 5: 68.9 vs 58.8 us per layer): two launches.
         self.one_launch_layers = self.num_heads == self.num_kv_heads and self._fills_the_chip(n_seqs * num_heads, device)
         self.last_layer_launches = None  # 1 / 2: which form utils.decode_layer_batched ran last (its docstring)
+        # decode_layer_batched: pools from this many pages per sequence up take the tiles launches (as InferenceController)
+        self.tiles_min_pages = getattr(self, "tiles_min_pages", 4097)
 
     @staticmethod
     def _fills_the_chip(workgroups: int, device) -> bool:

@@ -61,8 +61,9 @@ class BatchDecodeWithPagedKVCacheWrapper:
         self._wrapper.set_batch(n_seqs)
 
     def forward_fused_topk_batched(self, q, o, paged_kv_data, kv_tables, scores, state, max_n_scores: int,
-                                   budgets=None) -> None:
-        self._wrapper.forward_fused_topk_batched(q, o, paged_kv_data, kv_tables, scores, state, max_n_scores, budgets)
+                                   budgets=None, tiles: bool = False) -> bool:
+        return self._wrapper.forward_fused_topk_batched(q, o, paged_kv_data, kv_tables, scores, state, max_n_scores, budgets,
+                                                        tiles)
 
     def layer_fused_batched(self, k, v, metadata_data, meta_tables, q, o, paged_kv_data, kv_tables, state, max_n_scores: int,
                             budgets=None, scores_out=None) -> bool:

@@ -11,6 +11,7 @@ flash kernel of ``csrc/prefill.hip`` over the page table (no gathered K/V copy, 
 from __future__ import annotations
 
 import ctypes
+import os as _os
 
 import torch
 
@@ -18,11 +19,12 @@ from ._lib import Batch, PagedKV, check, lib
 
 _NHD, _HND = 0, 1
 
+STEP_STATE_INTS = 8      # int32 fields of quest_step_state_t
+QUEST_EUNSUPPORTED = -2  # include/quest_hip.h: no kernel for this plan / shape, nothing was launched
+
 # The reference compiles its argument validation in or out with -DBSK_TORCH_CHECK
 # (quest/ops/CMakeLists.txt:40); here QUEST_TORCH_CHECK=0 turns the same checks off at import time
 # (eager decode is host-bound: the checks are ~30 % of an op call's Python time).
-import os as _os
-
 _CHECKS_ON = _os.environ.get("QUEST_TORCH_CHECK", "1") != "0"
 
 
@@ -69,6 +71,14 @@ def _check_ge(a, b, what: str) -> None:
 def _check_half(x: torch.Tensor, op: str) -> None:
     if x.dtype != torch.float16:  # DISPATCH_PYTORCH_DTYPE_TO_CTYPE has only Half
         raise RuntimeError(f"{op} failed to dispatch with dtype {x.dtype}")
+
+
+def _launched(code: int, what: str) -> bool:
+    """False for QUEST_EUNSUPPORTED (nothing was launched: the caller takes its other route), else ``check``."""
+    if code == QUEST_EUNSUPPORTED:
+        return False
+    check(code, what)
+    return True
 
 
 _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -281,6 +291,12 @@ def _check_vec(x, n: int, name: str) -> None:
     _check_half(x, name)
 
 
+def _check_mat(x, n: int, cols: int, name: str) -> None:
+    _check_input(x, name)
+    _check_eq(x.numel(), n * cols, f"{name}.numel(), {n} * {cols}")
+    _check_half(x, name)
+
+
 def _check_weight(w, out_dim: int, in_dim: int, name: str) -> None:
     _check_input(w, name)
     _check_dim(2, w, name)
@@ -322,58 +338,46 @@ def decode_mlp_gate_up(h, gamma, eps: float, w_gate, w_up, act) -> None:
                                        act.data_ptr(), hidden, inter, _stream(h)), "decode_mlp_gate_up")
 
 
-def decode_qkv_rope(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, rope_scale: float, rope_theta: float,
-                    state) -> None:
-    """q ``[1, Hq, D]``, k / v ``[1, Hkv, D]`` = projections of ``rmsnorm(h; gamma, eps)`` with RoPE on q and k at the
-    position ``state.seq_len - 1`` (the device-resident step state, after ``step_state_advance``)."""
+def _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim: int, state, n: int):
+    """Validation and leading C arguments shared by the four ``decode_qkv_rope*`` launches; ``n`` tokens, ``state`` their
+    step state(s) ``[n, 8]`` int32."""
     hidden = wq.size(1)
-    _check_vec(h, hidden, "h")
+    _check_mat(h, n, hidden, "h")
     _check_vec(gamma, hidden, "gamma")
     _check_weight(wq, wq.size(0), hidden, "wq")
     _check_weight(wk, wk.size(0), hidden, "wk")
     _check_weight(wv, wk.size(0), hidden, "wv")
-    _check_vec(q, wq.size(0), "q")
-    _check_vec(k, wk.size(0), "k")
-    _check_vec(v, wk.size(0), "v")
+    _check_mat(q, n, wq.size(0), "q")
+    _check_mat(k, n, wk.size(0), "k")
+    _check_mat(v, n, wk.size(0), "v")
     _check_input(state, "state")
+    _check_eq(state.numel(), n * STEP_STATE_INTS, "states.numel(), n * 8")
     _check_eq(wq.size(0) % head_dim, 0, "wq.size(0) % head_dim, 0")
-    check(lib.quest_decode_qkv_rope(h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(), wk.data_ptr(),
-                                    wv.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), hidden,
-                                    wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim), float(rope_scale),
-                                    float(rope_theta), state.data_ptr(), _stream(h)), "decode_qkv_rope")
+    return (h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(), wk.data_ptr(), wv.data_ptr(), q.data_ptr(),
+            k.data_ptr(), v.data_ptr(), hidden, wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim))
+
+
+def decode_qkv_rope(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, rope_scale: float, rope_theta: float,
+                    state) -> None:
+    """q ``[1, Hq, D]``, k / v ``[1, Hkv, D]`` = projections of ``rmsnorm(h; gamma, eps)`` with RoPE on q and k at the
+    position ``state.seq_len - 1`` (the device-resident step state, after ``step_state_advance_batched``)."""
+    args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, state, 1)
+    check(lib.quest_decode_qkv_rope(*args, float(rope_scale), float(rope_theta), state.data_ptr(), _stream(h)),
+          "decode_qkv_rope")
 
 
 def decode_qkv_rope_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, inv_freq, attention_factor: float,
                           state) -> None:
     """``decode_qkv_rope`` with the RoPE frequency table of ``apply_rope_in_place_freqs`` (llama3 / yarn)."""
-    hidden = wq.size(1)
-    _check_vec(h, hidden, "h")
-    _check_vec(gamma, hidden, "gamma")
-    _check_weight(wq, wq.size(0), hidden, "wq")
-    _check_weight(wk, wk.size(0), hidden, "wk")
-    _check_weight(wv, wk.size(0), hidden, "wv")
-    _check_vec(q, wq.size(0), "q")
-    _check_vec(k, wk.size(0), "k")
-    _check_vec(v, wk.size(0), "v")
-    _check_input(state, "state")
-    _check_eq(wq.size(0) % head_dim, 0, "wq.size(0) % head_dim, 0")
+    args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, state, 1)
     _check_rope_table(inv_freq, head_dim)
-    check(lib.quest_decode_qkv_rope_freqs(h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(), wk.data_ptr(),
-                                          wv.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), hidden,
-                                          wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim),
-                                          inv_freq.data_ptr(), float(attention_factor), state.data_ptr(), _stream(h)),
-          "decode_qkv_rope_freqs")
+    check(lib.quest_decode_qkv_rope_freqs(*args, inv_freq.data_ptr(), float(attention_factor), state.data_ptr(),
+                                          _stream(h)), "decode_qkv_rope_freqs")
 
 
 # ---- the fused decode-layer launches for n <= 16 tokens (one per sequence of a batch)
 
 MAX_BATCHED_TOKENS = 16
-
-
-def _check_mat(x, n: int, cols: int, name: str) -> None:
-    _check_input(x, name)
-    _check_eq(x.numel(), n * cols, f"{name}.numel(), {n} * {cols}")
-    _check_half(x, name)
 
 
 def _check_tokens(n: int) -> None:
@@ -427,145 +431,42 @@ def decode_qkv_rope_batched(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim:
                             rope_theta: float, states) -> None:
     """q ``[n, Hq, D]``, k / v ``[n, Hkv, D]`` = projections of ``rmsnorm(h[i]; gamma, eps)``, RoPE on q and k at
     ``states[i].seq_len - 1`` (``states``: the batched step state ``[n, 8]`` int32)."""
-    hidden = wq.size(1)
-    n = h.numel() // hidden
+    n = h.numel() // wq.size(1)
     _check_tokens(n)
-    _check_mat(h, n, hidden, "h")
-    _check_vec(gamma, hidden, "gamma")
-    _check_weight(wq, wq.size(0), hidden, "wq")
-    _check_weight(wk, wk.size(0), hidden, "wk")
-    _check_weight(wv, wk.size(0), hidden, "wv")
-    _check_mat(q, n, wq.size(0), "q")
-    _check_mat(k, n, wk.size(0), "k")
-    _check_mat(v, n, wk.size(0), "v")
-    _check_input(states, "states")
-    _check_eq(states.numel(), n * STEP_STATE_INTS, "states.numel(), n * 8")
-    _check_eq(wq.size(0) % head_dim, 0, "wq.size(0) % head_dim, 0")
-    check(lib.quest_decode_qkv_rope_batched(h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(), wk.data_ptr(),
-                                            wv.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(), hidden,
-                                            wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim),
-                                            float(rope_scale), float(rope_theta), states.data_ptr(), n, _stream(h)),
-          "decode_qkv_rope_batched")
+    args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, states, n)
+    check(lib.quest_decode_qkv_rope_batched(*args, float(rope_scale), float(rope_theta), states.data_ptr(), n,
+                                            _stream(h)), "decode_qkv_rope_batched")
 
 
 def decode_qkv_rope_batched_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, inv_freq,
                                   attention_factor: float, states) -> None:
     """``decode_qkv_rope_batched`` with the RoPE frequency table of ``apply_rope_in_place_freqs`` (llama3 / yarn)."""
-    hidden = wq.size(1)
-    n = h.numel() // hidden
+    n = h.numel() // wq.size(1)
     _check_tokens(n)
-    _check_mat(h, n, hidden, "h")
-    _check_vec(gamma, hidden, "gamma")
-    _check_weight(wq, wq.size(0), hidden, "wq")
-    _check_weight(wk, wk.size(0), hidden, "wk")
-    _check_weight(wv, wk.size(0), hidden, "wv")
-    _check_mat(q, n, wq.size(0), "q")
-    _check_mat(k, n, wk.size(0), "k")
-    _check_mat(v, n, wk.size(0), "v")
-    _check_input(states, "states")
-    _check_eq(states.numel(), n * STEP_STATE_INTS, "states.numel(), n * 8")
-    _check_eq(wq.size(0) % head_dim, 0, "wq.size(0) % head_dim, 0")
+    args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, states, n)
     _check_rope_table(inv_freq, head_dim)
-    check(lib.quest_decode_qkv_rope_batched_freqs(h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(),
-                                                  wk.data_ptr(), wv.data_ptr(), q.data_ptr(), k.data_ptr(), v.data_ptr(),
-                                                  hidden, wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim),
-                                                  inv_freq.data_ptr(), float(attention_factor), states.data_ptr(), n,
-                                                  _stream(h)), "decode_qkv_rope_batched_freqs")
+    check(lib.quest_decode_qkv_rope_batched_freqs(*args, inv_freq.data_ptr(), float(attention_factor), states.data_ptr(),
+                                                  n, _stream(h)), "decode_qkv_rope_batched_freqs")
 
 
-# ---- state-driven (graph-replayable) forms: EXTENSIONS, see include/quest_hip.h quest_step_state_t
+# ---- state-driven (graph-replayable) forms: EXTENSIONS, see include/quest_hip.h quest_step_state_t.  One launch serves
+# the n sequences of a batch (SURVEY 8f-3, BASELINE config 5): the pools are shared, page tables are rows of ``[n, stride]``
+# int32 matrices, ``state`` is ``[n, 8]`` int32, q/k/v/o are ``[n, heads, dim]``, scores ``[n, Hq, stride]``.  A single
+# sequence is the batch of one and may come in its own shapes -- state ``[8]``, tables ``[capacity]``, scores
+# ``[Hq, stride]`` -- which reach the library as ``[1, ...]`` views of the same memory (a captured graph holds the addresses).
 
-STEP_STATE_INTS = 8  # int32 fields of quest_step_state_t
-
-
-def step_state_advance(state, kv_table, meta_table, page_size: int) -> None:
-    """Device-side prepare_metadata(1): ``state`` int32[8] (quest_step_state_t), tables int32 up to capacity."""
-    for t, n in ((state, "state"), (kv_table, "kv_table"), (meta_table, "meta_table")):
-        _check_input(t, n)
-        _check_eq(t.dtype, torch.int32, f"{n}.scalar_type(), torch::kInt32")
-    _check_eq(state.numel(), STEP_STATE_INTS, "state.numel(), 8")
-    check(lib.quest_step_state_advance(state.data_ptr(), kv_table.data_ptr(), meta_table.data_ptr(), int(page_size),
-                                       kv_table.numel(), meta_table.numel(), _stream(state)), "step_state_advance")
+def _lead(t, dims: int):
+    """``t`` as a ``dims``-D tensor: a view with a leading dimension of one where ``t`` has the single-sequence rank."""
+    return t.unsqueeze(0) if t is not None and t.dim() == dims - 1 else t
 
 
-def tile_max_offset(max_n: int) -> int:
-    """Column offset of the tile maxima in a score row of the tiles launches: the scores padded to 8 columns."""
-    return (int(max_n) + 7) // 8 * 8
-
-
-def tiles_row_stride(max_n: int) -> int:
-    """Smallest row stride (fp16 columns, a multiple of 8) of a score scratch that also holds the tile maxima."""
-    return (tile_max_offset(max_n) + ((int(max_n) + 7) // 8 + 3) // 4 * 4 + 7) // 8 * 8
-
-
-def append_estimate_dyn(k, v, kv_data, kv_table, q, o, metadata_data, meta_table, state, max_n_out: int,
-                        layout: int, tiles: bool = False) -> bool:
-    """append_estimate whose lengths / last-page ids / n_out come from ``state``; ``o`` is ``[Hq, stride]``.
-    ``tiles``: also store the rows' tile maxima (per 8 pages the largest score, as a 16-bit key) at column
-    ``tile_max_offset(max_n_out)`` -- ``o`` must be ``[Hq, >= tiles_row_stride(max_n_out)]``; returns False (nothing
-    launched) for QUEST_EUNSUPPORTED: no estimate tile of this shape is a multiple of 8 pages wide (checked before the
-    launch, ``csrc/estimate.hip`` ``launch_estimate``), or the group size / head_dim has no instantiation at all -- the
-    caller's whole-row launch (``tiles=False``) then raises for the latter."""
-    for t, n in ((k, "k"), (v, "v"), (kv_data, "kv_data"), (kv_table, "kv_table"), (q, "q"), (o, "o"),
-                 (metadata_data, "metadata_data"), (meta_table, "meta_table"), (state, "state")):
-        _check_input(t, n)
-    _check_dim(3, k, "k")
-    _check_dim(3, q, "q")
-    _check_dim(2, o, "o")
-    _check_eq(k.size(0), 1, "k.size(0), 1")
-    _check_eq(o.size(0), q.size(1), "o.size(0), num_heads")
-    _check_ge(o.size(1), max_n_out, "o.size(1), max_n_out")
-    _check_half(k, "Append_kv_cache_decode")
-    _check_half(q, "Estimate_attn_score")
-    kv = _paged(kv_data, kv_table, None, 1, 0, layout)
-    meta = _paged(metadata_data, meta_table, None, 1, 0, layout)
-    if tiles:
-        _check_ge(o.size(1), tiles_row_stride(max_n_out), "o.size(1), tiles_row_stride(max_n_out)")
-        code = lib.quest_append_estimate_tiles_dyn(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1),
-                                                   o.size(1), int(max_n_out), tile_max_offset(max_n_out), meta,
-                                                   state.data_ptr(), _stream(k))
-        if code == -2:
-            return False
-        check(code, "append_estimate_dyn")
-        return True
-    check(lib.quest_append_estimate_dyn(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1),
-                                        o.size(1), int(max_n_out), meta, state.data_ptr(), _stream(k)),
-          "append_estimate_dyn")
-    return True
-
-
-def append_kv_cache_decode_dyn(k, v, kv_data, kv_table, metadata_data, meta_table, state, layout: int) -> None:
-    """append_kv_cache_decode with lengths / last-page ids from ``state``."""
-    for t, n in ((k, "k"), (v, "v"), (kv_data, "kv_data"), (kv_table, "kv_table"), (metadata_data, "metadata_data"),
-                 (meta_table, "meta_table"), (state, "state")):
-        _check_input(t, n)
-    _check_eq(k.size(0), 1, "k.size(0), 1")
-    _check_half(k, "Append_kv_cache_decode")
-    kv = _paged(kv_data, kv_table, None, 1, 0, layout)
-    meta = _paged(metadata_data, meta_table, None, 1, 0, layout)
-    check(lib.quest_append_kv_cache_decode_dyn(k.data_ptr(), v.data_ptr(), kv, meta, state.data_ptr(), _stream(k)),
-          "Append_kv_cache_decode")
-
-
-def apply_rope_in_place_dyn(q, k, rope_scale: float, rope_theta: float, state) -> None:
-    _check_input(q, "q")
-    _check_input(k, "k")
-    _check_input(state, "state")
-    _check_eq(q.size(0), 1, "q.size(0), 1")
-    _check_half(q, "apply_rope_in_place")
-    check(lib.quest_apply_rope_in_place_dyn(q.data_ptr(), k.data_ptr(), q.size(1), k.size(1), q.size(2),
-                                            float(rope_scale), float(rope_theta), state.data_ptr(), _stream(q)),
-          "apply_rope_in_place_dyn")
-
-
-# ---------------------------------------------------------------------------------------------------------
-# Batched state-driven step (EXTENSION; SURVEY 8f-3, BASELINE config 5): n sequences per launch.  The pools
-# are shared, page tables are rows of ``[n, stride]`` int32 matrices, ``state`` is ``[n, 8]`` int32,
-# q/k/v/o are ``[n, heads, dim]``, scores ``[n, Hq, stride]``.
 def _batch(state, kv_tables, meta_tables, budgets=None) -> Batch:
-    """quest_batch_t.  ``budgets``: optional int32 ``[n]`` device tensor of per-sequence page budgets (pages a sequence
-    attends INCLUDING its current one); None = the budget the handler was planned with, for every sequence."""
+    """quest_batch_t of ``state`` ``[n, 8]`` (or ``[8]``: one sequence, tables ``[capacity]``).  ``budgets``: optional int32
+    ``[n]`` device tensor of per-sequence page budgets (pages a sequence attends INCLUDING its current one); None = the
+    budget the handler was planned with, for every sequence."""
+    state, kv_tables, meta_tables = _lead(state, 2), _lead(kv_tables, 2), _lead(meta_tables, 2)
     _check_dim(2, state, "state")
+    _check_eq(state.size(1), STEP_STATE_INTS, "state.size(-1), 8")
     n = state.size(0)
     if budgets is not None:
         _check_input(budgets, "page_budgets")
@@ -586,23 +487,40 @@ def _batch(state, kv_tables, meta_tables, budgets=None) -> Batch:
 
 
 def step_state_advance_batched(state, kv_tables, meta_tables, page_size: int) -> None:
+    """Device-side prepare_metadata(1) of every sequence: ``state`` int32 ``[n, 8]`` (quest_step_state_t), tables int32
+    ``[n, capacity]``."""
     _check_input(state, "state")
+    _check_eq(state.dtype, torch.int32, "state.scalar_type(), torch::kInt32")
     b = _batch(state, kv_tables, meta_tables)
     check(lib.quest_step_state_advance_batched(state.data_ptr(), kv_tables.data_ptr(), meta_tables.data_ptr(),
-                                               int(page_size), kv_tables.size(1), meta_tables.size(1), b,
+                                               int(page_size), kv_tables.size(-1), meta_tables.size(-1), b,
                                                _stream(state)), "step_state_advance_batched")
+
+
+def tile_max_offset(max_n: int) -> int:
+    """Column offset of the tile maxima in a score row of the tiles launches: the scores padded to 8 columns."""
+    return (int(max_n) + 7) // 8 * 8
+
+
+def tiles_row_stride(max_n: int) -> int:
+    """Smallest row stride (fp16 columns, a multiple of 8) of a score scratch that also holds the tile maxima."""
+    return (tile_max_offset(max_n) + ((int(max_n) + 7) // 8 + 3) // 4 * 4 + 7) // 8 * 8
 
 
 def append_estimate_batched(k, v, kv_data, kv_tables, q, o, metadata_data, meta_tables, state, max_n_out: int,
                             layout: int, tiles: bool = False) -> bool:
-    """``append_estimate_dyn`` for ``n`` sequences in one launch: k/v ``[n, Hkv, D]``, q ``[n, Hq, D]``, o ``[n, Hq, stride]``.
-    ``tiles``: every row also gets its tile maxima at column ``tile_max_offset(max_n_out)`` (``o.size(2)`` must be at
-    least ``tiles_row_stride(max_n_out)``); returns False (nothing launched) for QUEST_EUNSUPPORTED, as
-    ``append_estimate_dyn`` does -- the caller then issues the whole-row launch (``tiles=False``)."""
+    """append_estimate for ``n`` sequences in one launch, lengths / last-page ids / n_out read from ``state``: k/v
+    ``[n, Hkv, D]``, q ``[n, Hq, D]``, o ``[n, Hq, stride]``.
+    ``tiles``: every row also gets its tile maxima (per 8 pages the largest score, as a 16-bit key) at column
+    ``tile_max_offset(max_n_out)`` -- ``o.size(-1)`` must be at least ``tiles_row_stride(max_n_out)``; returns False
+    (nothing launched) for QUEST_EUNSUPPORTED: no estimate tile of this shape is a multiple of 8 pages wide (checked before
+    the launch, ``csrc/estimate.hip`` ``launch_estimate``), or the group size / head_dim has no instantiation at all -- the
+    caller's whole-row launch (``tiles=False``) then raises for the latter."""
     for t, n in ((k, "k"), (v, "v"), (kv_data, "kv_data"), (q, "q"), (o, "o"), (metadata_data, "metadata_data"),
                  (state, "state")):
         _check_input(t, n)
     b = _batch(state, kv_tables, meta_tables)
+    o = _lead(o, 3)
     _check_dim(3, k, "k")
     _check_dim(3, q, "q")
     _check_dim(3, o, "o")
@@ -617,17 +535,19 @@ def append_estimate_batched(k, v, kv_data, kv_tables, q, o, metadata_data, meta_
     meta = _paged(metadata_data, meta_tables, None, 1, 0, layout)
     if tiles:
         _check_ge(o.size(2), tiles_row_stride(max_n_out), "o.size(2), tiles_row_stride(max_n_out)")
-        code = lib.quest_append_estimate_tiles_batched(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1),
-                                                       o.size(2), int(max_n_out), tile_max_offset(max_n_out), meta,
-                                                       state.data_ptr(), b, _stream(k))
-        if code == -2:
-            return False
-        check(code, "append_estimate_batched")
-        return True
+        return _launched(lib.quest_append_estimate_tiles_batched(
+            k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1), o.size(2), int(max_n_out),
+            tile_max_offset(max_n_out), meta, state.data_ptr(), b, _stream(k)), "append_estimate_batched")
     check(lib.quest_append_estimate_batched(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1),
                                             o.size(2), int(max_n_out), meta, state.data_ptr(), b, _stream(k)),
           "append_estimate_batched")
     return True
+
+
+def append_estimate_dyn(k, v, kv_data, kv_table, q, o, metadata_data, meta_table, state, max_n_out: int,
+                        layout: int, tiles: bool = False) -> bool:
+    """``append_estimate_batched`` under its single-sequence name: k/v/q ``[1, H, D]``, ``o`` ``[Hq, stride]``, state ``[8]``."""
+    return append_estimate_batched(k, v, kv_data, kv_table, q, o, metadata_data, meta_table, state, max_n_out, layout, tiles)
 
 
 def estimate_attn_score_batched(q, o, metadata_data, meta_tables, state, max_n_out: int, layout: int) -> None:
@@ -672,6 +592,7 @@ def topk_filtering_batched(scores, kv_tables, d_out, indices_out, state, max_num
 
 
 def append_kv_cache_decode_batched(k, v, kv_data, kv_tables, metadata_data, meta_tables, state, layout: int) -> None:
+    """append_kv_cache_decode of one token per sequence, lengths / last-page ids from ``state``: k, v ``[n, Hkv, D]``."""
     for t, n in ((k, "k"), (v, "v"), (kv_data, "kv_data"), (metadata_data, "metadata_data"), (state, "state")):
         _check_input(t, n)
     b = _batch(state, kv_tables, meta_tables)
@@ -684,6 +605,7 @@ def append_kv_cache_decode_batched(k, v, kv_data, kv_tables, metadata_data, meta
 
 
 def apply_rope_in_place_batched(q, k, rope_scale: float, rope_theta: float, state) -> None:
+    """apply_rope_in_place with row i of q ``[n, Hq, D]`` / k ``[n, Hkv, D]`` at position ``state[i].seq_len - 1``."""
     _check_input(q, "q")
     _check_input(k, "k")
     _check_input(state, "state")
@@ -789,11 +711,8 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_eq(page_list.dtype, torch.int32, "page_list.scalar_type(), torch::kInt32")
         _check_half(q, "BatchDecodeWithPagedKVCache")
         kv = _paged(paged_kv_data, page_list, None, paged_kv_last_page_len, paged_kv_last_page_idx, self._layout)
-        code = lib.quest_decode_forward_shared(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), None, _stream(q))
-        if code == -2:
-            return False
-        check(code, "BatchDecodeWithPagedKVCache")
-        return True
+        return _launched(lib.quest_decode_forward_shared(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), None,
+                                                         _stream(q)), "BatchDecodeWithPagedKVCache")
 
     def forward_fused_topk(self, q, o, paged_kv_data, page_table, scores, topk_val_out, topk_idx_out,
                            paged_kv_last_page_len: int, paged_kv_last_page_idx: int) -> bool:
@@ -814,46 +733,39 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_half(q, "BatchDecodeWithPagedKVCache")
         _check_half(scores, "BatchDecodeWithPagedKVCache")
         kv = _paged(paged_kv_data, page_table, None, paged_kv_last_page_len, paged_kv_last_page_idx, self._layout)
-        code = lib.quest_decode_forward_fused_topk_strided(
+        # (QUEST_EUNSUPPORTED: chunk larger than the fused front end stages)
+        return _launched(lib.quest_decode_forward_fused_topk_strided(
             self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), scores.data_ptr(), scores.size(1), scores.stride(0),
             topk_val_out.data_ptr() if topk_val_out is not None else None,
-            topk_idx_out.data_ptr() if topk_idx_out is not None else None, None, _stream(q))
-        if code == -2:  # QUEST_EUNSUPPORTED: chunk larger than the fused front end stages
-            return False
-        check(code, "BatchDecodeWithPagedKVCache")
-        return True
+            topk_idx_out.data_ptr() if topk_idx_out is not None else None, None, _stream(q)), "BatchDecodeWithPagedKVCache")
+
+    # ---- state-driven launches (see the free functions above): n sequences per launch, one sequence = the batch of one in
+    # its own shapes (state ``[8]``, tables ``[capacity]``, scores ``[Hq, stride]``)
+    def set_batch(self, n_seqs: int) -> None:
+        """Sequences per launch the NEXT begin_forward plans for (workspace, work split)."""
+        check(lib.quest_decode_set_batch(self._h, int(n_seqs)), "set_batch")
+
+    def forward_shared_batched(self, q, o, paged_kv_data, kv_tables, state) -> None:
+        """forward_shared over all pages of every sequence, live lengths from ``state`` (graph replay): q/o ``[n, Hq, D]``."""
+        for t, n in ((q, "q"), (o, "o"), (paged_kv_data, "paged_kv_data"), (state, "state")):
+            _check_input(t, n)
+        b = _batch(state, kv_tables, None)
+        _check_dim(3, q, "q")
+        _check_eq(q.size(0), b.n_seqs, "q.size(0), n_seqs")
+        _check_half(q, "BatchDecodeWithPagedKVCache")
+        kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
+        check(lib.quest_decode_forward_shared_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
+                                                      state.data_ptr(), b, None, _stream(q)),
+              "BatchDecodeWithPagedKVCache")
 
     def forward_shared_dyn(self, q, o, paged_kv_data, page_table, state) -> None:
-        """forward_shared over all pages of the sequence, live length from ``state`` (graph replay)."""
-        for t, n in ((q, "q"), (o, "o"), (paged_kv_data, "paged_kv_data"), (page_table, "page_table"), (state, "state")):
-            _check_input(t, n)
-        _check_half(q, "BatchDecodeWithPagedKVCache")
-        kv = _paged(paged_kv_data, page_table, None, 1, 0, self._layout)
-        check(lib.quest_decode_forward_shared_dyn(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), state.data_ptr(),
-                                                  None, _stream(q)), "BatchDecodeWithPagedKVCache")
-
-    def append_forward_shared_dyn(self, k, v, metadata_data, meta_table, q, o, paged_kv_data, page_table, state) -> bool:
-        """``append_kv_cache_decode_dyn`` + ``forward_shared_dyn`` in ONE launch (the new token's row is taken from k / v
-        by the workgroup that attends the current page, written to the pool and folded into the metadata there).  False
-        when the shape is outside the group-shared kernel: the caller issues the two launches."""
-        for t, n in ((k, "k"), (v, "v"), (metadata_data, "metadata_data"), (meta_table, "meta_table"), (q, "q"), (o, "o"),
-                     (paged_kv_data, "paged_kv_data"), (page_table, "page_table"), (state, "state")):
-            _check_input(t, n)
-        _check_half(q, "BatchDecodeWithPagedKVCache")
-        _check_half(k, "BatchDecodeWithPagedKVCache")
-        _check_eq(tuple(k.shape), tuple(v.shape), "k.shape, v.shape")
-        kv = _paged(paged_kv_data, page_table, None, 1, 0, self._layout)
-        _check_eq(tuple(k.shape[-2:]), (kv.num_heads, kv.head_dim), "k.shape[-2:], (kv heads, head_dim)")
-        meta = _paged(metadata_data, meta_table, None, 1, 0, self._layout)
-        code = lib.quest_decode_append_forward_shared_dyn(self._h, k.data_ptr(), v.data_ptr(), meta, q.data_ptr(), o.data_ptr(),
-                                                          kv, q.size(1), state.data_ptr(), None, _stream(q))
-        if code == -2:
-            return False
-        check(code, "BatchDecodeWithPagedKVCache")
-        return True
+        """``forward_shared_batched`` under its single-sequence name."""
+        self.forward_shared_batched(q, o, paged_kv_data, page_table, state)
 
     def append_forward_shared_batched(self, k, v, metadata_data, meta_tables, q, o, paged_kv_data, kv_tables, state) -> bool:
-        """``append_forward_shared_dyn`` for every sequence of a batch (k, v ``[n, Hkv, D]``)."""
+        """``append_kv_cache_decode_batched`` + ``forward_shared_batched`` in ONE launch (k, v ``[n, Hkv, D]``; the new
+        token's row is taken from k / v by the workgroup that attends the current page, written to the pool and folded into
+        the metadata there).  False when the shape is outside the group-shared kernel: the caller issues the two launches."""
         for t, n in ((k, "k"), (v, "v"), (metadata_data, "metadata_data"), (q, "q"), (o, "o"),
                      (paged_kv_data, "paged_kv_data"), (state, "state")):
             _check_input(t, n)
@@ -867,46 +779,13 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
         _check_eq(tuple(k.shape[-2:]), (kv.num_heads, kv.head_dim), "k.shape[-2:], (kv heads, head_dim)")
         meta = _paged(metadata_data, meta_tables, None, 1, 0, self._layout)
-        code = lib.quest_decode_append_forward_shared_batched(self._h, k.data_ptr(), v.data_ptr(), meta, q.data_ptr(),
-                                                              o.data_ptr(), kv, q.size(1), state.data_ptr(), b, None, _stream(q))
-        if code == -2:
-            return False
-        check(code, "BatchDecodeWithPagedKVCache")
-        return True
+        return _launched(lib.quest_decode_append_forward_shared_batched(
+            self._h, k.data_ptr(), v.data_ptr(), meta, q.data_ptr(), o.data_ptr(), kv, q.size(1), state.data_ptr(), b, None,
+            _stream(q)), "BatchDecodeWithPagedKVCache")
 
-    def forward_fused_topk_dyn(self, q, o, paged_kv_data, page_table, scores, state, max_n_scores: int,
-                               tiles: bool = False) -> bool:
-        """forward_fused_topk whose row length and current page come from ``state`` (graph replay).
-        ``tiles``: the rows carry their tile maxima (``append_estimate_dyn(..., tiles=True)`` wrote them): two short
-        selection passes instead of passes over the whole row; returns False (nothing launched) where the plan is
-        outside what the tiles launch serves (more than 256 selected pages, page size != 16)."""
-        for t, n in ((q, "q"), (o, "o"), (paged_kv_data, "paged_kv_data"), (page_table, "page_table"),
-                     (scores, "scores"), (state, "state")):
-            _check_input(t, n)
-        _check_dim(2, scores, "scores")
-        _check_eq(scores.size(0), q.size(1), "scores.size(0), num_qo_heads")
-        _check_ge(scores.size(1), max_n_scores, "scores.size(1), max_n_scores")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
-        kv = _paged(paged_kv_data, page_table, None, 1, 0, self._layout)
-        if tiles:
-            _check_ge(scores.size(1), tiles_row_stride(max_n_scores), "scores.size(1), tiles_row_stride(max_n_scores)")
-            code = lib.quest_decode_forward_fused_topk_tiles_dyn(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
-                                                                 scores.data_ptr(), scores.size(1), int(max_n_scores),
-                                                                 tile_max_offset(max_n_scores), state.data_ptr(), None,
-                                                                 _stream(q))
-            if code == -2:
-                return False
-            check(code, "BatchDecodeWithPagedKVCache")
-            return True
-        check(lib.quest_decode_forward_fused_topk_dyn(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
-                                                      scores.data_ptr(), scores.size(1), int(max_n_scores),
-                                                      state.data_ptr(), None, _stream(q)),
-              "BatchDecodeWithPagedKVCache")
-        return True
-
-    def set_batch(self, n_seqs: int) -> None:
-        """Sequences per launch the NEXT begin_forward plans for (workspace, work split)."""
-        check(lib.quest_decode_set_batch(self._h, int(n_seqs)), "set_batch")
+    def append_forward_shared_dyn(self, k, v, metadata_data, meta_table, q, o, paged_kv_data, page_table, state) -> bool:
+        """``append_forward_shared_batched`` under its single-sequence name."""
+        return self.append_forward_shared_batched(k, v, metadata_data, meta_table, q, o, paged_kv_data, page_table, state)
 
     def forward_batched(self, q, o, paged_kv_data, indices, state, budgets=None) -> None:
         """forward for ``n`` sequences in one launch: q/o ``[n, Hq, D]``, indices ``[n, Hq, k_max]`` (int32) of which
@@ -928,12 +807,15 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
 
     def forward_fused_topk_batched(self, q, o, paged_kv_data, kv_tables, scores, state, max_n_scores: int,
                                    budgets=None, tiles: bool = False) -> bool:
-        """forward_fused_topk_dyn for ``n`` sequences in one launch: q/o ``[n, Hq, D]``, scores ``[n, Hq, stride]``.
-        ``tiles``: the rows carry their tile maxima (``append_estimate_batched(..., tiles=True)`` wrote them); returns
-        False (nothing launched) where the plan is outside what the tiles launch serves, as ``forward_fused_topk_dyn``."""
+        """forward_fused_topk for ``n`` sequences in one launch, row lengths and current pages from ``state`` (graph
+        replay): q/o ``[n, Hq, D]``, scores ``[n, Hq, stride]``.
+        ``tiles``: the rows carry their tile maxima (``append_estimate_batched(..., tiles=True)`` wrote them): two short
+        selection passes instead of passes over the whole row; returns False (nothing launched) where the plan is
+        outside what the tiles launch serves (more than 256 selected pages, page size != 16)."""
         for t, n in ((q, "q"), (o, "o"), (paged_kv_data, "paged_kv_data"), (scores, "scores"), (state, "state")):
             _check_input(t, n)
         b = _batch(state, kv_tables, None, budgets)
+        scores = _lead(scores, 3)
         _check_dim(3, q, "q")
         _check_dim(3, scores, "scores")
         _check_eq(q.size(0), b.n_seqs, "q.size(0), n_seqs")
@@ -944,19 +826,19 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
         if tiles:
             _check_ge(scores.size(2), tiles_row_stride(max_n_scores), "scores.size(2), tiles_row_stride(max_n_scores)")
-            code = lib.quest_decode_forward_fused_topk_tiles_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
-                                                                     scores.data_ptr(), scores.size(2), int(max_n_scores),
-                                                                     tile_max_offset(max_n_scores), state.data_ptr(), b,
-                                                                     None, _stream(q))
-            if code == -2:
-                return False
-            check(code, "BatchDecodeWithPagedKVCache")
-            return True
+            return _launched(lib.quest_decode_forward_fused_topk_tiles_batched(
+                self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), scores.data_ptr(), scores.size(2), int(max_n_scores),
+                tile_max_offset(max_n_scores), state.data_ptr(), b, None, _stream(q)), "BatchDecodeWithPagedKVCache")
         check(lib.quest_decode_forward_fused_topk_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
                                                           scores.data_ptr(), scores.size(2), int(max_n_scores),
                                                           state.data_ptr(), b, None, _stream(q)),
               "BatchDecodeWithPagedKVCache")
         return True
+
+    def forward_fused_topk_dyn(self, q, o, paged_kv_data, page_table, scores, state, max_n_scores: int,
+                               tiles: bool = False) -> bool:
+        """``forward_fused_topk_batched`` under its single-sequence name: ``scores`` ``[Hq, stride]``, state ``[8]``."""
+        return self.forward_fused_topk_batched(q, o, paged_kv_data, page_table, scores, state, max_n_scores, tiles=tiles)
 
     def layer_fused_batched(self, k, v, metadata_data, meta_tables, q, o, paged_kv_data, kv_tables, state,
                             max_n_scores: int, budgets=None, scores_out=None) -> bool:
@@ -981,31 +863,16 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         meta = _paged(metadata_data, meta_tables, None, 1, 0, self._layout)
         sc_ptr, sc_stride = None, 0
         if scores_out is not None:
+            scores_out = _lead(scores_out, 3)
             _check_input(scores_out, "scores_out")
             _check_dim(3, scores_out, "scores_out")
             _check_eq(tuple(scores_out.shape[:2]), tuple(q.shape[:2]), "scores_out.shape[:2], (n_seqs, num_qo_heads)")
             _check_ge(scores_out.size(2), max_n_scores, "scores_out.size(2), max_n_scores")
             _check_half(scores_out, "BatchDecodeWithPagedKVCache")
             sc_ptr, sc_stride = scores_out.data_ptr(), scores_out.size(2)
-        code = lib.quest_decode_layer_fused_batched(self._h, k.data_ptr(), v.data_ptr(), meta, q.data_ptr(), o.data_ptr(), kv,
-                                                    q.size(1), int(max_n_scores), state.data_ptr(), b, sc_ptr, sc_stride,
-                                                    None, _stream(q))
-        if code == -2:
-            return False
-        check(code, "BatchDecodeWithPagedKVCache")
-        return True
-
-    def forward_shared_batched(self, q, o, paged_kv_data, kv_tables, state) -> None:
-        for t, n in ((q, "q"), (o, "o"), (paged_kv_data, "paged_kv_data"), (state, "state")):
-            _check_input(t, n)
-        b = _batch(state, kv_tables, None)
-        _check_dim(3, q, "q")
-        _check_eq(q.size(0), b.n_seqs, "q.size(0), n_seqs")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
-        kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
-        check(lib.quest_decode_forward_shared_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
-                                                      state.data_ptr(), b, None, _stream(q)),
-              "BatchDecodeWithPagedKVCache")
+        return _launched(lib.quest_decode_layer_fused_batched(
+            self._h, k.data_ptr(), v.data_ptr(), meta, q.data_ptr(), o.data_ptr(), kv, q.size(1), int(max_n_scores),
+            state.data_ptr(), b, sc_ptr, sc_stride, None, _stream(q)), "BatchDecodeWithPagedKVCache")
 
     # introspection used by the bench / tuning sweeps (not part of the reference surface)
     def plan_info(self):
@@ -1048,21 +915,16 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
               "set_selection_out")
 
     def arm_step_advance(self, state, kv_tables, meta_tables, page_size: int) -> None:
-        """The NEXT token's reservation (``step_state_advance``) rides in this handler's next forward call: in its merge
+        """The NEXT token's reservation (``step_state_advance_batched``) rides in this handler's next forward call: in its merge
         launch where the plan has one, as its own launch behind the attention kernel otherwise.  ``state`` is the step state
         ``[8]`` (one sequence, tables ``[capacity]``) or ``[n, 8]`` (tables ``[n, capacity]``).  Call right before the LAST
-        layer's forward of a step whose first token was reserved by ``step_state_advance`` (quest_hip.h)."""
-        for t, n in ((state, "state"), (kv_tables, "kv_tables"), (meta_tables, "meta_tables")):
-            _check_input(t, n)
-            _check_eq(t.dtype, torch.int32, f"{n}.scalar_type(), torch::kInt32")
-        if state.dim() == 1:
-            b = Batch(1, 0, 0, 0, None)
-            max_kv, max_meta = kv_tables.numel(), meta_tables.numel()
-        else:
-            b = _batch(state, kv_tables, meta_tables)
-            max_kv, max_meta = kv_tables.size(1), meta_tables.size(1)
+        layer's forward of a step whose first token was reserved by ``step_state_advance_batched`` (quest_hip.h)."""
+        _check_input(state, "state")
+        _check_eq(state.dtype, torch.int32, "state.scalar_type(), torch::kInt32")
+        b = _batch(state, kv_tables, meta_tables)
         check(lib.quest_decode_arm_step_advance(self._h, state.data_ptr(), kv_tables.data_ptr(), meta_tables.data_ptr(),
-                                                int(page_size), max_kv, max_meta, b), "arm_step_advance")
+                                                int(page_size), kv_tables.size(-1), meta_tables.size(-1), b),
+              "arm_step_advance")
 
     def set_skip_merge(self, skip: bool) -> None:
         """Measurement aid: launch only the attention kernel (partial states stay unmerged, ``o`` unwritten)."""

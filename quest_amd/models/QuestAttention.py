@@ -126,40 +126,22 @@ class QuestAttention(nn.Module):
         nvtx.range_pop()
         return out, None, past_key_value
 
-    def forward_dyn(self, hidden_states: torch.Tensor, iController: qutils.InferenceController, scores: torch.Tensor,
-                    dense: bool) -> torch.Tensor:
+    def forward_state(self, hidden_states: torch.Tensor, controller, scores: torch.Tensor, dense: bool) -> torch.Tensor:
         """Decode-token forward whose every length comes from the controller's device-resident step state
         (``enable_device_state`` + ``begin_graph_decode(dense_layers=True)``), so a whole model step can be
-        captured in one hipGraph and replayed as the sequence grows.  ``dense``: full-KV layer (the model's
-        first layers) vs Quest sparse layer.  EXTENSION of the reference module."""
-        bsz, q_len, _ = hidden_states.size()
-        assert bsz == 1 and q_len == 1
-        q = self.q_proj(hidden_states).view(1, self.num_heads, self.head_dim)
-        k = self.k_proj(hidden_states).view(1, self.num_key_value_heads, self.head_dim)
-        v = self.v_proj(hidden_states).view(1, self.num_key_value_heads, self.head_dim)
-        if dense:
-            attn = qutils.decode_layer_dense_dyn(q, k, v, iController, self.layer_idx, self.rope_scale, self.rope_theta,
-                                                 apply_rope=True, rope_freqs=self.rotary(q.device))
-        else:
-            attn = qutils.decode_layer_dyn(q, k, v, iController, self.layer_idx, scores, self.rope_scale,
-                                           self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device))
-        return self.o_proj(attn.reshape(1, 1, self.hidden_size))
-
-
-    def forward_batched(self, hidden_states: torch.Tensor, bController: "qutils.BatchedInferenceController",
-                        scores: torch.Tensor, dense: bool) -> torch.Tensor:
-        """``forward_dyn`` for ``n`` sequences at once: ``hidden_states`` is ``[n, 1, hidden]`` (one decode token
-        per sequence), all sequences share the controller's pools and every op is ONE launch for the batch
-        (``quest_amd.utils.decode_layer_batched``).  EXTENSION: the reference module asserts batch size 1."""
+        captured in one hipGraph and replayed as the sequences grow.  ``hidden_states`` is ``[n, 1, hidden]``, one decode
+        token per sequence of ``controller`` -- a ``BatchedInferenceController`` (shared pools, every op ONE launch for
+        the batch) or an ``InferenceController``, the batch of one.  ``dense``: full-KV layer (the model's first layers)
+        vs Quest sparse layer.  EXTENSION: the reference module asserts batch size 1 and plans every token on the host."""
         n, q_len, _ = hidden_states.size()
-        assert q_len == 1 and n == bController.n_seqs
+        assert q_len == 1 and n == controller.n_seqs
         q = self.q_proj(hidden_states).view(n, self.num_heads, self.head_dim)
         k = self.k_proj(hidden_states).view(n, self.num_key_value_heads, self.head_dim)
         v = self.v_proj(hidden_states).view(n, self.num_key_value_heads, self.head_dim)
         if dense:
-            attn = qutils.decode_layer_dense_batched(q, k, v, bController, self.layer_idx, self.rope_scale,
+            attn = qutils.decode_layer_dense_batched(q, k, v, controller, self.layer_idx, self.rope_scale,
                                                      self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device))
         else:
-            attn = qutils.decode_layer_batched(q, k, v, bController, self.layer_idx, scores, self.rope_scale,
+            attn = qutils.decode_layer_batched(q, k, v, controller, self.layer_idx, scores, self.rope_scale,
                                                self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device))
         return self.o_proj(attn.reshape(n, 1, self.hidden_size))

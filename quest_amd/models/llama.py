@@ -17,6 +17,7 @@ from typing import Optional
 import torch
 from torch import nn
 
+from .. import _kernels
 from .. import utils as qutils
 from . import rope as rope_mod
 from .QuestAttention import QuestAttention
@@ -107,70 +108,46 @@ class LlamaDecoderLayer(nn.Module):
         hidden_states = hidden_states + h
         return hidden_states + self.mlp(self.post_attention_layernorm(hidden_states))
 
-    def forward_dyn(self, hidden_states: torch.Tensor, iController, scores, dense: bool) -> torch.Tensor:
-        h = self.self_attn.forward_dyn(self.input_layernorm(hidden_states), iController, scores, dense)
+    def forward_state(self, hidden_states: torch.Tensor, controller, scores, dense: bool) -> torch.Tensor:
+        """State-driven decode token of every sequence of ``controller`` (``QuestAttention.forward_state``)."""
+        h = self.self_attn.forward_state(self.input_layernorm(hidden_states), controller, scores, dense)
         hidden_states = hidden_states + h
         return hidden_states + self.mlp(self.post_attention_layernorm(hidden_states))
 
-
-    def forward_batched(self, hidden_states: torch.Tensor, bController, scores, dense: bool) -> torch.Tensor:
-        h = self.self_attn.forward_batched(self.input_layernorm(hidden_states), bController, scores, dense)
-        hidden_states = hidden_states + h
-        return hidden_states + self.mlp(self.post_attention_layernorm(hidden_states))
-
-    def forward_dyn_fused(self, h: torch.Tensor, iController, scores, dense: bool, ws: "DecodeWorkspace") -> torch.Tensor:
-        """``forward_dyn`` in 4 launches besides the attention's: RMSNorm + q/k/v projections + RoPE, o_proj + residual,
-        RMSNorm + gate/up + SiLU*up, down_proj + residual (csrc/decode_layer.hip; EXTENSION).  ``h`` ``[hidden]`` is the
-        residual stream, updated IN PLACE; batch 1, fp16."""
-        from .. import _kernels
-
+    def forward_state_fused(self, h: torch.Tensor, controller, scores, dense: bool, ws: "DecodeWorkspace") -> torch.Tensor:
+        """``forward_state`` in 4 launches besides the attention's: RMSNorm + q/k/v projections + RoPE, o_proj + residual,
+        RMSNorm + gate/up + SiLU*up, down_proj + residual (csrc/decode_layer.hip; EXTENSION).  ``h`` is the residual stream,
+        updated IN PLACE; fp16.  An ``InferenceController`` takes the batch-1 launches (``h`` ``[hidden]``), a
+        ``BatchedInferenceController`` the n-token ones at every n <= 16 (``h`` ``[n, hidden]``; the weights are read once
+        per batch: persist_kernel) -- different kernels, whose results differ in the last bits."""
         a, m = self.self_attn, self.mlp
+        qkv_rope, qkv_rope_freqs, gemv_residual, mlp_gate_up = _fused_layer_launches(controller)[:4]
         freqs = a.rotary(h.device)
+        qkv = (h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon, a.q_proj.weight, a.k_proj.weight,
+               a.v_proj.weight, ws.q, ws.k, ws.v, a.head_dim)
         if freqs is None:
-            _kernels.decode_qkv_rope(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon, a.q_proj.weight,
-                                     a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v, a.head_dim, a.rope_scale,
-                                     a.rope_theta, iController.step_state)
+            qkv_rope(*qkv, a.rope_scale, a.rope_theta, controller.step_states)
         else:
-            _kernels.decode_qkv_rope_freqs(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon,
-                                           a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v, a.head_dim,
-                                           freqs[0], freqs[1], iController.step_state)
+            qkv_rope_freqs(*qkv, freqs[0], freqs[1], controller.step_states)
         if dense:
-            attn = qutils.decode_layer_dense_dyn(ws.q, ws.k, ws.v, iController, a.layer_idx)
+            attn = qutils.decode_layer_dense_batched(ws.q, ws.k, ws.v, controller, a.layer_idx, out=ws.attn)
         else:
-            attn = qutils.decode_layer_dyn(ws.q, ws.k, ws.v, iController, a.layer_idx, scores)
-        _kernels.decode_gemv_residual(attn, a.o_proj.weight, h)
-        _kernels.decode_mlp_gate_up(h, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon,
-                                    m.gate_proj.weight, m.up_proj.weight, ws.act)
-        _kernels.decode_gemv_residual(ws.act, m.down_proj.weight, h)
+            attn = qutils.decode_layer_batched(ws.q, ws.k, ws.v, controller, a.layer_idx, scores, out=ws.attn)
+        gemv_residual(attn, a.o_proj.weight, h)
+        mlp_gate_up(h, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon,
+                    m.gate_proj.weight, m.up_proj.weight, ws.act)
+        gemv_residual(ws.act, m.down_proj.weight, h)
         return h
 
 
-    def forward_batched_fused(self, h: torch.Tensor, bController, scores, dense: bool, ws: "DecodeWorkspace") -> torch.Tensor:
-        """``forward_batched`` with the same 4 fused launches per layer as ``forward_dyn_fused``, each for all ``n``
-        tokens at once (the weights are read once per batch: csrc/decode_layer.hip persist_kernel).  ``h`` ``[n, hidden]``
-        is the residual stream, updated IN PLACE; fp16, n <= 16."""
-        from .. import _kernels
-
-        a, m = self.self_attn, self.mlp
-        freqs = a.rotary(h.device)
-        if freqs is None:
-            _kernels.decode_qkv_rope_batched(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon,
-                                             a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v,
-                                             a.head_dim, a.rope_scale, a.rope_theta, bController.step_states)
-        else:
-            _kernels.decode_qkv_rope_batched_freqs(h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon,
-                                                   a.q_proj.weight, a.k_proj.weight, a.v_proj.weight, ws.q, ws.k, ws.v,
-                                                   a.head_dim, freqs[0], freqs[1], bController.step_states)
-        if dense:
-            attn = qutils.decode_layer_dense_batched(ws.q, ws.k, ws.v, bController, a.layer_idx, out=ws.attn)
-        else:
-            attn = qutils.decode_layer_batched(ws.q, ws.k, ws.v, bController, a.layer_idx, scores, out=ws.attn)
-        _kernels.decode_gemv_residual_batched(attn, a.o_proj.weight, h)
-        _kernels.decode_mlp_gate_up_batched(h, self.post_attention_layernorm.weight,
-                                            self.post_attention_layernorm.variance_epsilon, m.gate_proj.weight,
-                                            m.up_proj.weight, ws.act)
-        _kernels.decode_gemv_residual_batched(ws.act, m.down_proj.weight, h)
-        return h
+def _fused_layer_launches(controller):
+    """The projection launches of the fused decoder layer and of the final norm + lm_head for ``controller``'s kind: (q/k/v
+    + RoPE by formula, by frequency table, GEMV + residual, MLP gate/up, norm + GEMV)."""
+    if isinstance(controller, qutils.BatchedInferenceController):
+        return (_kernels.decode_qkv_rope_batched, _kernels.decode_qkv_rope_batched_freqs,
+                _kernels.decode_gemv_residual_batched, _kernels.decode_mlp_gate_up_batched, _kernels.decode_norm_gemv_batched)
+    return (_kernels.decode_qkv_rope, _kernels.decode_qkv_rope_freqs, _kernels.decode_gemv_residual,
+            _kernels.decode_mlp_gate_up, _kernels.decode_norm_gemv)
 
 
 def fused_layer_launches_supported(config, n_tokens: int) -> bool:
@@ -234,43 +211,22 @@ class LlamaModel(nn.Module):
         return self.norm(h)
 
 
-    def forward_decode_dyn(self, h: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
-        """One decode token with no host-side planning: the device-side state advance replaces
-        prepare_metadata / begin_forward / end_forward (capturable, replayable)."""
-        ctl = self.iController
-        qutils.step_advance_dyn(ctl)
+    def forward_decode(self, h: torch.Tensor, scores: torch.Tensor, controller) -> torch.Tensor:
+        """One decode token of every sequence of ``controller`` (``h``: ``[n, 1, hidden]``) with no host-side planning:
+        the device-side state advance replaces prepare_metadata / begin_forward / end_forward (capturable, replayable)."""
+        qutils.step_advance_batched(controller)
         for idx, layer in enumerate(self.layers):
-            h = layer.forward_dyn(h, ctl, scores, dense=idx < self._quest_skip_layer)
+            h = layer.forward_state(h, controller, scores, dense=idx < self._quest_skip_layer)
         return self.norm(h)
 
-
-    def forward_decode_dyn_fused(self, h: torch.Tensor, scores: torch.Tensor, ws: DecodeWorkspace) -> torch.Tensor:
-        """``forward_decode_dyn`` with the fused decode layer; returns the residual stream ``[hidden]`` BEFORE the final
-        norm (the caller fuses that into its lm_head launch)."""
-        ctl = self.iController
-        qutils.step_advance_dyn(ctl)
-        ws.h.copy_(h.reshape(-1))
-        for idx, layer in enumerate(self.layers):
-            layer.forward_dyn_fused(ws.h, ctl, scores, idx < self._quest_skip_layer, ws)
-        return ws.h
-
-    def forward_decode_batched_fused(self, h: torch.Tensor, scores: torch.Tensor, ws: DecodeWorkspace) -> torch.Tensor:
-        """``forward_decode_batched`` with the fused n-token decoder layers; returns the residual stream ``[n, hidden]``
-        BEFORE the final norm (fused into the caller's lm_head launch)."""
-        b = self.bController
-        qutils.step_advance_batched(b)
+    def forward_decode_fused(self, h: torch.Tensor, scores: torch.Tensor, controller, ws: DecodeWorkspace) -> torch.Tensor:
+        """``forward_decode`` with the fused decoder layers; returns the residual stream (``ws.h``: ``[hidden]`` or
+        ``[n, hidden]``) BEFORE the final norm (the caller fuses that into its lm_head launch)."""
+        qutils.step_advance_batched(controller)
         ws.h.copy_(h.reshape(ws.h.shape))
         for idx, layer in enumerate(self.layers):
-            layer.forward_batched_fused(ws.h, b, scores, idx < self._quest_skip_layer, ws)
+            layer.forward_state_fused(ws.h, controller, scores, idx < self._quest_skip_layer, ws)
         return ws.h
-
-    def forward_decode_batched(self, h: torch.Tensor, scores: torch.Tensor) -> torch.Tensor:
-        """One decode token of every sequence of ``self.bController`` (``h``: ``[n, 1, hidden]``)."""
-        b = self.bController
-        qutils.step_advance_batched(b)
-        for idx, layer in enumerate(self.layers):
-            h = layer.forward_batched(h, b, scores, dense=idx < self._quest_skip_layer)
-        return self.norm(h)
 
 
 class LlamaForCausalLM(nn.Module):
@@ -423,48 +379,54 @@ class LlamaForCausalLM(nn.Module):
         sparse layers attend all of them, like the reference's full-attention branch).  The
         graph reads its input from ``self.graph_input`` ``[1, 1, hidden]`` and leaves the logits in
         ``self.graph_logits``; sequence lengths live on the device (EXTENSION)."""
-        m, ctl = self.model, self.model.iController
+        ctl = self.model.iController
+        ctl.set_page_budget(self.model._quest_page_budget)
+        self._capture_decode_graph(ctl, fused_layers)
+
+    def _capture_decode_graph(self, ctl, fused_layers: Optional[bool]) -> None:
+        """Capture one decode step of every sequence of ``ctl`` (an ``InferenceController`` is the batch of one)."""
+        m, n = self.model, ctl.n_seqs
         dev = next(self.parameters()).device
-        ctl.set_page_budget(m._quest_page_budget)
         ctl.enable_device_state()
         ctl.begin_graph_decode(dense_layers=m._quest_skip_layer > 0)
-        self.graph_input = torch.zeros(1, 1, self.config.hidden_size, dtype=self.lm_head.weight.dtype, device=dev)
+        self.graph_input = torch.zeros(n, 1, self.config.hidden_size, dtype=self.lm_head.weight.dtype, device=dev)
         self._graph_scores = qutils.score_scratch(ctl)
         if fused_layers is None:
             import os
 
             fused_layers = os.environ.get("QUEST_FUSED_LAYER", "1") != "0"
-        fused_layers = (fused_layers and self.lm_head.weight.dtype == torch.float16
-                        and fused_layer_launches_supported(self.config, 1))
+        fused_layers = (fused_layers and self.lm_head.weight.dtype == torch.float16 and n <= _kernels.MAX_BATCHED_TOKENS
+                        and fused_layer_launches_supported(self.config, n))
         self.fused_layers = fused_layers
         if fused_layers:
-            from .. import _kernels
-
             # (kept on self: the captured launches hold these buffers' addresses)
-            ws = self._graph_ws = DecodeWorkspace(self.config, torch.float16, dev)
-            logits = torch.empty(1, 1, self.config.vocab_size, dtype=torch.float16, device=dev)
+            ws = self._graph_ws = DecodeWorkspace(self.config, torch.float16, dev, n)
+            logits = torch.empty(n, 1, self.config.vocab_size, dtype=torch.float16, device=dev)
+            norm_gemv = _fused_layer_launches(ctl)[4]
 
             def step():
-                hs = m.forward_decode_dyn_fused(self.graph_input, self._graph_scores, ws)
-                _kernels.decode_norm_gemv(hs, m.norm.weight, m.norm.variance_epsilon, self.lm_head.weight, logits)
+                hs = m.forward_decode_fused(self.graph_input, self._graph_scores, ctl, ws)
+                norm_gemv(hs, m.norm.weight, m.norm.variance_epsilon, self.lm_head.weight, logits)
                 return logits
         else:
             def step():
-                return self.lm_head(m.forward_decode_dyn(self.graph_input, self._graph_scores))
+                return self.lm_head(m.forward_decode(self.graph_input, self._graph_scores, ctl))
 
         # Warm-up (allocator, rocBLAS workspaces) runs a real step on a dummy input: it advances the device
-        # state and folds the dummy key into the current page's (max, min) metadata entry.  K/V bytes it wrote
+        # state and folds the dummy key into every sequence's current (max, min) metadata entry.  K/V bytes it wrote
         # are overwritten by the first real token, but the metadata fold is not idempotent -> snapshot the
-        # current metadata page of every layer and restore it, then rewind the state.
-        meta_page = ctl.metadata_cache.indicies[-1]
-        saved = ctl.metadata_cache.pool.buf[:, meta_page].clone()
+        # current metadata page(s) of every layer and restore them, then rewind the state.
+        seqs = getattr(ctl, "seqs", [ctl])
+        pool = seqs[0].metadata_cache.pool  # (one pool for all sequences of a batch)
+        pages = torch.tensor([c.metadata_cache.indicies[-1] for c in seqs], device=dev)
+        saved = pool.buf[:, pages].clone()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.inference_mode():
             step()
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
-        ctl.metadata_cache.pool.buf[:, meta_page].copy_(saved)
+        pool.buf[:, pages] = saved
         ctl.sync_device_state()
         self._graph = torch.cuda.CUDAGraph()
         with torch.inference_mode(), torch.cuda.graph(self._graph):
@@ -483,7 +445,6 @@ class LlamaForCausalLM(nn.Module):
         self._graph.replay()
         self.model.iController.prepare_metadata(1)  # host mirror of the device-side reservation
         return self.graph_logits
-
 
     # ------------------------------------------------------------------ batched serving (EXTENSION)
     def quest_init_batched(self, n_seqs: int, page_size: int, max_seq_len: int, token_budget: int = 512,
@@ -514,50 +475,7 @@ class LlamaForCausalLM(nn.Module):
         """Batched ``capture_decode_graph``: input ``self.graph_input`` ``[n, 1, hidden]``, logits
         ``self.graph_logits`` ``[n, 1, vocab]``.  ``fused_layers`` as in ``capture_decode_graph`` (default on for fp16
         models and n <= 16 unless ``QUEST_FUSED_LAYER=0``): 4 fused launches per layer for the whole batch."""
-        m, b = self.model, self.model.bController
-        dev = next(self.parameters()).device
-        b.enable_device_state()
-        b.begin_graph_decode(dense_layers=m._quest_skip_layer > 0)
-        n = b.n_seqs
-        self.graph_input = torch.zeros(n, 1, self.config.hidden_size, dtype=self.lm_head.weight.dtype, device=dev)
-        self._graph_scores = qutils.score_scratch(b)
-        if fused_layers is None:
-            import os
-
-            fused_layers = os.environ.get("QUEST_FUSED_LAYER", "1") != "0"
-        from .. import _kernels
-
-        fused_layers = (fused_layers and self.lm_head.weight.dtype == torch.float16 and n <= _kernels.MAX_BATCHED_TOKENS
-                        and fused_layer_launches_supported(self.config, n))
-        self.fused_layers = fused_layers
-        if fused_layers:
-            ws = self._graph_ws = DecodeWorkspace(self.config, torch.float16, dev, n)  # (kept: the graph holds its addresses)
-            logits = torch.empty(n, 1, self.config.vocab_size, dtype=torch.float16, device=dev)
-
-            def step():
-                hs = m.forward_decode_batched_fused(self.graph_input, self._graph_scores, ws)
-                _kernels.decode_norm_gemv_batched(hs, m.norm.weight, m.norm.variance_epsilon, self.lm_head.weight, logits)
-                return logits
-        else:
-            def step():
-                return self.lm_head(m.forward_decode_batched(self.graph_input, self._graph_scores))
-
-        # warm-up folds a dummy key into every sequence's current metadata entry: snapshot / restore those
-        # pages (see capture_decode_graph)
-        pages = torch.tensor([c.metadata_cache.indicies[-1] for c in b.seqs], device=dev)
-        saved = b.metadata_pool.buf[:, pages].clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), torch.inference_mode():
-            step()
-        torch.cuda.current_stream().wait_stream(side)
-        torch.cuda.synchronize()
-        b.metadata_pool.buf[:, pages] = saved
-        b.sync_device_state()
-        self._graph = torch.cuda.CUDAGraph()
-        with torch.inference_mode(), torch.cuda.graph(self._graph):
-            self.graph_logits = step()
-        self._graph_epoch = b.state_epoch
+        self._capture_decode_graph(self.model.bController, fused_layers)
 
     def decode_graph_step_batched(self, input_ids: torch.Tensor) -> torch.Tensor:
         """One token for every sequence: ``input_ids`` ``[n]`` -> logits ``[n, 1, vocab]`` (the graph's buffer)."""

@@ -189,8 +189,7 @@ def score_scratch(controller) -> torch.Tensor:
     stride = (controller.max_pages + 7) // 8 * 8
     # room for the rows' tile maxima behind the scores (long-row launches, ``decode_layer_dyn``); a batch gets it only
     # where ``decode_layer_batched`` would take the tiles launches, shorter batched scratches keep their shape
-    if not isinstance(controller, BatchedInferenceController) or \
-            controller.max_pages - 1 >= getattr(controller, "tiles_min_pages", 4097):
+    if not isinstance(controller, BatchedInferenceController) or controller.max_pages - 1 >= controller.tiles_min_pages:
         stride = max(stride, _kernels.tiles_row_stride(controller.max_pages - 1))
     shape = (controller.num_heads, stride)
     if isinstance(controller, BatchedInferenceController):
@@ -201,22 +200,17 @@ def score_scratch(controller) -> torch.Tensor:
 def _need_state(controller) -> None:
     """The state-driven ops read lengths and page tables from device memory: `enable_device_state()` must have been
     called after the prefill (and again after `clean_states()` / `quest_clear()`, which drop it)."""
-    state = getattr(controller, "step_state", None) if not isinstance(controller, BatchedInferenceController) \
-        else getattr(controller, "step_states", None)
-    if state is None:
+    if getattr(controller, "step_states", None) is None:
         raise RuntimeError("the controller has no device-resident step state: call enable_device_state() after the "
                            "prefill (clean_states() / quest_clear() drop it)")
 
 
-def _rope_dyn(q, k, rope_scale, rope_theta, rope_freqs, state) -> None:
-    if rope_freqs is not None:
-        _kernels.apply_rope_in_place_freqs(q, k, rope_freqs[0], rope_freqs[1], states=state)
-        return
-    scale, theta = _rope_defaults(rope_scale, rope_theta)
-    _kernels.apply_rope_in_place_dyn(q, k, scale, theta, state)
+# One body per operator, written for the n sequences of a ``BatchedInferenceController`` (grid.z = sequence; q/k/v are
+# ``[n_seqs, heads, dim]``); an ``InferenceController`` presents itself as the batch of one (``step_states``,
+# ``kv_tables``, ``meta_tables``, ``kv_layer``: controller.py), so the ``*_dyn`` and ``*_batched`` names below reach the
+# same launches.
 
-
-def _rope_batched(q, k, rope_scale, rope_theta, rope_freqs, states) -> None:
+def _rope_at_state(q, k, rope_scale, rope_theta, rope_freqs, states) -> None:
     if rope_freqs is not None:
         _kernels.apply_rope_in_place_freqs(q, k, rope_freqs[0], rope_freqs[1], states=states)
         return
@@ -224,10 +218,69 @@ def _rope_batched(q, k, rope_scale, rope_theta, rope_freqs, states) -> None:
     _kernels.apply_rope_in_place_batched(q, k, scale, theta, states)
 
 
+def _step_advance(ctl) -> None:
+    _need_state(ctl)
+    _kernels.step_state_advance_batched(ctl.step_states, ctl.kv_tables, ctl.meta_tables, ctl.page_size)
+
+
+def _decode_layer(q, k, v, ctl, layer_idx, scores, rope_scale, rope_theta, apply_rope, rope_freqs, tiles, out=None,
+                  one_launch=None, write_scores=False, advance_after=False) -> torch.Tensor:
+    """[RoPE] -> append+estimate -> top-k+attention (+merge) for every sequence of ``ctl``, the optional one-launch form
+    first: ``decode_layer_dyn`` / ``decode_layer_batched`` describe the arguments."""
+    _need_state(ctl)
+    handler = ctl._decode_handler
+    if advance_after:
+        handler.arm_step_advance(ctl.step_states, ctl.kv_tables, ctl.meta_tables, ctl.page_size)
+    if apply_rope:
+        _rope_at_state(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_states)
+    max_n = ctl.max_pages - 1
+    kvb, mb = ctl.kv_layer(layer_idx), ctl.metadata_layer(layer_idx)
+    o = torch.empty_like(q) if out is None else out
+    if (ctl.one_launch_layers if one_launch is None else one_launch):
+        if handler.layer_fused_batched(k, v, mb, ctl.meta_tables, q, o, kvb, ctl.kv_tables, ctl.step_states, max_n,
+                                       ctl.page_budgets, scores if write_scores else None):
+            ctl.last_layer_launches = 1
+            return o
+        if one_launch:
+            raise RuntimeError("the one-launch layer does not serve this plan / shape (needs one workgroup per head, "
+                               "page_size 16, head_dim 64 / 128, <= 255 selected pages, rows <= 4096 pages)")
+    # long rows: the estimate hands the rows' tile maxima (per 8 pages the largest score) to the attention launch, which
+    # then selects in two short passes (csrc/decode_device.cuh sparse_decode_tiles_body); same selection, same outputs.
+    # Where either tiles launch does not serve the plan or shape (it returns False) the whole-row launch runs instead.
+    tiles = (tiles if tiles is not None else max_n >= ctl.tiles_min_pages) \
+        and scores.size(-1) >= _kernels.tiles_row_stride(max_n) and ctl.inference_page_budget - 1 <= 256
+    estimate = (k, v, kvb, ctl.kv_tables, q, scores, mb, ctl.meta_tables, ctl.step_states, max_n, ctl.layout)
+    attend = (q, o, kvb, ctl.kv_tables, scores, ctl.step_states, max_n, ctl.page_budgets)
+    tiles = tiles and _kernels.append_estimate_batched(*estimate, tiles=True)
+    if not tiles:
+        _kernels.append_estimate_batched(*estimate)
+    if not (tiles and handler.forward_fused_topk_batched(*attend, tiles=True)):
+        handler.forward_fused_topk_batched(*attend)
+    ctl.last_layer_launches = 2
+    return o
+
+
+def _decode_layer_dense(q, k, v, ctl, layer_idx, rope_scale, rope_theta, apply_rope, rope_freqs, fuse_append, out=None,
+                        advance_after=False) -> torch.Tensor:
+    """[RoPE] -> append + attention over all pages (+merge) for every sequence of ``ctl``: ``decode_layer_dense_dyn``."""
+    _need_state(ctl)
+    handler = ctl._dense_handler
+    if apply_rope:
+        _rope_at_state(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_states)
+    o = torch.empty_like(q) if out is None else out
+    kvb, mb = ctl.kv_layer(layer_idx), ctl.metadata_layer(layer_idx)
+    if advance_after:
+        handler.arm_step_advance(ctl.step_states, ctl.kv_tables, ctl.meta_tables, ctl.page_size)
+    if not (fuse_append and handler.append_forward_shared_batched(k, v, mb, ctl.meta_tables, q, o, kvb, ctl.kv_tables,
+                                                                  ctl.step_states)):
+        _kernels.append_kv_cache_decode_batched(k, v, kvb, ctl.kv_tables, mb, ctl.meta_tables, ctl.step_states, ctl.layout)
+        handler.forward_shared_batched(q, o, kvb, ctl.kv_tables, ctl.step_states)
+    return o
+
+
 def step_advance_dyn(iController: InferenceController) -> None:
-    _need_state(iController)
-    _kernels.step_state_advance(iController.step_state, iController.kv_table_full, iController.meta_table_full,
-                                iController.page_size)
+    """Device-side ``prepare_metadata(1)``: reserve the next token in the step state and the page tables."""
+    _step_advance(iController)
 
 
 def decode_layer_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iController: InferenceController,
@@ -243,30 +296,8 @@ def decode_layer_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iControl
     merge launch instead of heading the next step as a launch of its own (the first token is reserved by one
     ``step_advance_dyn`` before the first step; the host mirror ``prepare_metadata(1)`` follows every step as before).
     ``rope_freqs``: the frequency-table RoPE of ``apply_rope_in_place`` (llama3 / yarn configs)."""
-    ctl = iController
-    _need_state(ctl)
-    if advance_after:
-        ctl._decode_handler.arm_step_advance(ctl.step_state, ctl.kv_table_full, ctl.meta_table_full, ctl.page_size)
-    if apply_rope:
-        _rope_dyn(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_state)
-    max_n = ctl.max_pages - 1
-    # long rows: the estimate hands the rows' tile maxima (per 8 pages the largest score) to the attention launch, which
-    # then selects in two short passes (csrc/decode_device.cuh sparse_decode_tiles_body); same selection, same outputs
-    tiles = (tiles if tiles is not None else max_n >= ctl.tiles_min_pages) and scores.dim() == 2 \
-        and scores.size(1) >= _kernels.tiles_row_stride(max_n) and ctl.inference_page_budget - 1 <= 256
-    tiles = _kernels.append_estimate_dyn(k, v, ctl.kv_cache.buf_layer(layer_idx), ctl.kv_table_full, q, scores,
-                                         ctl.metadata_cache.buf_layer(layer_idx), ctl.meta_table_full, ctl.step_state,
-                                         max_n, ctl.layout, tiles=True) if tiles else False
-    if not tiles:
-        _kernels.append_estimate_dyn(k, v, ctl.kv_cache.buf_layer(layer_idx), ctl.kv_table_full, q, scores,
-                                     ctl.metadata_cache.buf_layer(layer_idx), ctl.meta_table_full, ctl.step_state, max_n,
-                                     ctl.layout)
-    o = torch.empty_like(q)
-    if not (tiles and ctl._decode_handler.forward_fused_topk_dyn(q, o, ctl.kv_cache.buf_layer(layer_idx), ctl.kv_table_full,
-                                                                 scores, ctl.step_state, max_n, tiles=True)):
-        ctl._decode_handler.forward_fused_topk_dyn(q, o, ctl.kv_cache.buf_layer(layer_idx), ctl.kv_table_full, scores,
-                                                   ctl.step_state, max_n)
-    return o
+    return _decode_layer(q, k, v, iController, layer_idx, scores, rope_scale, rope_theta, apply_rope, rope_freqs, tiles,
+                         advance_after=advance_after)
 
 
 def decode_layer_dense_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iController: InferenceController,
@@ -277,29 +308,12 @@ def decode_layer_dense_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iC
     [RoPE] -> append + attention over all pages in ONE launch (group-shared kernel; the workgroup that attends the
     current page takes the new token from k / v, writes it to the pool and folds it into the metadata) (+merge).  Shapes
     outside the group-shared kernel take the separate append launch.  Needs ``begin_graph_decode(dense_layers=True)``."""
-    ctl = iController
-    _need_state(ctl)
-    if apply_rope:
-        _rope_dyn(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_state)
-    o = torch.empty_like(q)
-    kvb, mb = ctl.kv_cache.buf_layer(layer_idx), ctl.metadata_cache.buf_layer(layer_idx)
-    if advance_after:
-        ctl._dense_handler.arm_step_advance(ctl.step_state, ctl.kv_table_full, ctl.meta_table_full, ctl.page_size)
-    if not (fuse_append and ctl._dense_handler.append_forward_shared_dyn(k, v, mb, ctl.meta_table_full, q, o, kvb,
-                                                                         ctl.kv_table_full, ctl.step_state)):
-        _kernels.append_kv_cache_decode_dyn(k, v, kvb, ctl.kv_table_full, mb, ctl.meta_table_full, ctl.step_state, ctl.layout)
-        ctl._dense_handler.forward_shared_dyn(q, o, kvb, ctl.kv_table_full, ctl.step_state)
-    return o
+    return _decode_layer_dense(q, k, v, iController, layer_idx, rope_scale, rope_theta, apply_rope, rope_freqs, fuse_append,
+                               advance_after=advance_after)
 
-
-
-# --------------------------------------------------------------------------------------------------
-# Batched state-driven step: the same three launches per layer serve every sequence of a
-# ``BatchedInferenceController`` (grid.z = sequence).  q/k/v are ``[n_seqs, heads, dim]``.
 
 def step_advance_batched(bController: BatchedInferenceController) -> None:
-    _kernels.step_state_advance_batched(bController.step_states, bController.kv_tables, bController.meta_tables,
-                                        bController.page_size)
+    _step_advance(bController)
 
 
 def decode_layer_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bController: BatchedInferenceController,
@@ -327,36 +341,18 @@ def decode_layer_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bCon
     MHA batches that fill the chip) ``scores`` keeps whatever it held before unless ``write_scores=True``; code that reads
     the scratch after this call must pass ``write_scores=True`` or ``one_launch=False``.  Which form ran is left in
     ``bController.last_layer_launches`` (1 or 2)."""
-    b = bController
-    _need_state(b)
-    if apply_rope:
-        _rope_batched(q, k, rope_scale, rope_theta, rope_freqs, b.step_states)
-    max_n = b.max_pages - 1
-    if (b.one_launch_layers if one_launch is None else one_launch):
-        o = torch.empty_like(q) if out is None else out
-        if b._decode_handler.layer_fused_batched(k, v, b.metadata_layer(layer_idx), b.meta_tables, q, o, b.kv_layer(layer_idx),
-                                                 b.kv_tables, b.step_states, max_n, b.page_budgets,
-                                                 scores if write_scores else None):
-            b.last_layer_launches = 1
-            return o
-        if one_launch:
-            raise RuntimeError("the one-launch layer does not serve this plan / shape (needs one workgroup per head, "
-                               "page_size 16, head_dim 64 / 128, <= 255 selected pages, rows <= 4096 pages)")
-    # long rows: tile maxima handed from the estimate to the attention launch, as in decode_layer_dyn
-    tiles = (tiles if tiles is not None else max_n >= getattr(b, "tiles_min_pages", 4097)) and scores.dim() == 3 \
-        and scores.size(2) >= _kernels.tiles_row_stride(max_n) and b.inference_page_budget - 1 <= 256
-    tiles = _kernels.append_estimate_batched(k, v, b.kv_layer(layer_idx), b.kv_tables, q, scores, b.metadata_layer(layer_idx),
-                                             b.meta_tables, b.step_states, max_n, b.layout, tiles=True) if tiles else False
-    if not tiles:
-        _kernels.append_estimate_batched(k, v, b.kv_layer(layer_idx), b.kv_tables, q, scores, b.metadata_layer(layer_idx),
-                                         b.meta_tables, b.step_states, max_n, b.layout)
-    o = torch.empty_like(q) if out is None else out
-    if not (tiles and b._decode_handler.forward_fused_topk_batched(q, o, b.kv_layer(layer_idx), b.kv_tables, scores,
-                                                                   b.step_states, max_n, b.page_budgets, tiles=True)):
-        b._decode_handler.forward_fused_topk_batched(q, o, b.kv_layer(layer_idx), b.kv_tables, scores, b.step_states, max_n,
-                                                     b.page_budgets)
-    b.last_layer_launches = 2
-    return o
+    return _decode_layer(q, k, v, bController, layer_idx, scores, rope_scale, rope_theta, apply_rope, rope_freqs, tiles,
+                         out=out, one_launch=one_launch, write_scores=write_scores)
+
+
+def decode_layer_dense_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
+                               bController: BatchedInferenceController, layer_idx: int,
+                               rope_scale: Optional[float] = None, rope_theta: Optional[float] = None,
+                               apply_rope: bool = False, out: Optional[torch.Tensor] = None,
+                               fuse_append: bool = True, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
+    """``decode_layer_dense_dyn`` for every sequence at once (needs ``begin_graph_decode(dense_layers=True)``)."""
+    return _decode_layer_dense(q, k, v, bController, layer_idx, rope_scale, rope_theta, apply_rope, rope_freqs, fuse_append,
+                               out=out)
 
 
 # ---- the reference's four operators of a decode step, one by one, for a whole batch (eager: no captured graph needed;
@@ -399,23 +395,4 @@ def decode_sparse_attn_batched(q: torch.Tensor, bController: BatchedInferenceCon
     _need_state(b)
     o = torch.empty_like(q) if out is None else out
     b._decode_handler.forward_batched(q, o, b.kv_layer(layer_idx), topk_indices, b.step_states, b.page_budgets)
-    return o
-
-
-def decode_layer_dense_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
-                               bController: BatchedInferenceController, layer_idx: int,
-                               rope_scale: Optional[float] = None, rope_theta: Optional[float] = None,
-                               apply_rope: bool = False, out: Optional[torch.Tensor] = None,
-                               fuse_append: bool = True, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
-    """``decode_layer_dense_dyn`` for every sequence at once (needs ``begin_graph_decode(dense_layers=True)``)."""
-    b = bController
-    _need_state(b)
-    if apply_rope:
-        _rope_batched(q, k, rope_scale, rope_theta, rope_freqs, b.step_states)
-    o = torch.empty_like(q) if out is None else out
-    kvb, mb = b.kv_layer(layer_idx), b.metadata_layer(layer_idx)
-    if not (fuse_append and b._dense_handler.append_forward_shared_batched(k, v, mb, b.meta_tables, q, o, kvb, b.kv_tables,
-                                                                           b.step_states)):
-        _kernels.append_kv_cache_decode_batched(k, v, kvb, b.kv_tables, mb, b.meta_tables, b.step_states, b.layout)
-        b._dense_handler.forward_shared_batched(q, o, kvb, b.kv_tables, b.step_states)
     return o

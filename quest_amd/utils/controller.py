@@ -23,7 +23,41 @@ from .kv_cache import KvCache
 from .utils import TensorLayout
 
 
+# State-driven sparse layers (``quest_amd.utils.decode_layer_dyn`` / ``decode_layer_batched``): pools from this many pages
+# per sequence up take the tiles launches (tile maxima handed from the estimate to the attention launch); below, every
+# workgroup of a head selects over the whole row.  A controller's ``tiles_min_pages`` overrides it.
+TILES_MIN_PAGES = 4097
+
+
+def _state_row(c: "InferenceController"):
+    """quest_step_state_t (include/quest_hip.h) of one sequence's caches, as its 8 ints."""
+    kv, meta = c.kv_cache, c.metadata_cache
+    return [kv.seqlen, len(kv.indicies), kv.last_page_len, kv.indicies[-1], len(meta.indicies), meta.last_page_len,
+            meta.indicies[-1], 0]
+
+
+def _plan_graph_handlers(ctl, budget: int, dense_layers: bool) -> None:
+    """Plan ``ctl``'s sparse handler for ``budget`` pages and, with ``dense_layers``, a second handler for full-KV layers
+    over the per-sequence capacity -- once, for launches that will be replayed over many tokens."""
+    plans = [(ctl._decode_handler, budget)]
+    if dense_layers:
+        if ctl._dense_handler is None:
+            ctl._dense_handler = BatchDecodeWithPagedKVCacheWrapper(kv_layout=TensorLayout.FORMAT2STR[ctl.layout])
+        plans.append((ctl._dense_handler, ctl.max_pages))
+    for handler, pages in plans:
+        handler.set_batch(ctl.n_seqs)
+        handler.begin_forward(torch.tensor([0, pages - 1], dtype=torch.int32), ctl.num_heads, ctl.num_kv_heads,
+                              ctl.head_dim, ctl.page_size, ctl.dtype)
+
+
 class InferenceController:
+    # what a state-driven launch reads (quest_amd.utils.decode_layer_*): the sequence is a batch of one, with no
+    # per-sequence budgets and no one-launch layers (that form needs a batch that fills the chip)
+    n_seqs = 1
+    page_budgets = None
+    one_launch_layers = False
+    tiles_min_pages = TILES_MIN_PAGES
+
     def __init__(self, num_layers, num_heads, head_dim, page_size,
                  page_budget,  # pages, including the last (current) page
                  max_seq_len,  # capacity of the KV / metadata pools, in tokens
@@ -49,6 +83,7 @@ class InferenceController:
 
         self._page_budget = page_budget
         self._decode_handler = BatchDecodeWithPagedKVCacheWrapper(kv_layout=TensorLayout.FORMAT2STR[self.layout])
+        self._dense_handler = None  # planned by begin_graph_decode(dense_layers=True)
 
         self.kv_indices_with_last = None
         self.kv_indices_without_last = None
@@ -70,6 +105,7 @@ class InferenceController:
         self._topk_buffers: Dict[int, Tuple[torch.Tensor, torch.Tensor]] = {}
         # device-resident step state (enable_device_state); state_epoch changes whenever graphs captured over it go stale
         self.kv_table_full = self.meta_table_full = self.step_state = None
+        self.kv_tables = self.meta_tables = self.step_states = None  # the same three as the one-row matrices of a batch
         self.state_epoch = 0
 
     # ------------------------------------------------------------------ budgets
@@ -148,14 +184,14 @@ class InferenceController:
         """Put the sequence's step state (lengths, last-page ids) in device memory so that a decode step
         captured in a hipGraph can be replayed while the sequence grows (EXTENSION).  Call
         after prefill; the state describes the cache BEFORE the next token -- the graph's first node,
-        ``_kernels.step_state_advance``, moves it forward by one token on the device."""
+        ``_kernels.step_state_advance_batched``, moves it forward by one token on the device."""
         self.kv_table_full = self.kv_cache.full_device_table()
         self.meta_table_full = self.metadata_cache.full_device_table()
         self.max_pages = self.kv_table_full.numel()
-        # decode_layer_dyn: pools from this many pages up take the tiles launches (tile maxima handed from the estimate
-        # to the attention launch); below, every workgroup of a head selects over the whole row
-        self.tiles_min_pages = getattr(self, "tiles_min_pages", 4097)
         self.step_state = torch.zeros(8, dtype=torch.int32, device=self.device)
+        # the same memory as the one-row matrices of a batch (views: a captured graph holds the addresses)
+        self.kv_tables, self.meta_tables = self.kv_table_full.view(1, -1), self.meta_table_full.view(1, -1)
+        self.step_states = self.step_state.view(1, -1)
         self.state_epoch += 1  # graphs captured before this call are stale
         self.sync_device_state()
 
@@ -168,21 +204,17 @@ class InferenceController:
         # of its pages (k = n), which is the reference's full-attention branch (QuestAttention.py:123-132), and
         # moves into the sparse regime by itself as the sequence grows -- same graph.
         assert len(self.kv_cache.indicies) >= 1, "prefill first"
-        budget = min(self._page_budget, self.max_pages)
-        self.inference_page_budget = budget
-        self._decode_handler.begin_forward(torch.tensor([0, budget - 1], dtype=torch.int32), self.num_heads,
-                                           self.num_kv_heads, self.head_dim, self.page_size, self.dtype)
-        if dense_layers:
-            if getattr(self, "_dense_handler", None) is None:
-                self._dense_handler = BatchDecodeWithPagedKVCacheWrapper(kv_layout=TensorLayout.FORMAT2STR[self.layout])
-            self._dense_handler.begin_forward(torch.tensor([0, self.max_pages - 1], dtype=torch.int32), self.num_heads,
-                                              self.num_kv_heads, self.head_dim, self.page_size, self.dtype)
+        self.inference_page_budget = min(self._page_budget, self.max_pages)
+        _plan_graph_handlers(self, self.inference_page_budget, dense_layers)
 
     def sync_device_state(self) -> None:
-        kv, meta = self.kv_cache, self.metadata_cache
-        host = torch.tensor([kv.seqlen, len(kv.indicies), kv.last_page_len, kv.indicies[-1], len(meta.indicies),
-                             meta.last_page_len, meta.indicies[-1], 0], dtype=torch.int32)
-        self.step_state.copy_(host)
+        self.step_state.copy_(torch.tensor(_state_row(self), dtype=torch.int32))
+
+    def kv_layer(self, layer_idx: int) -> torch.Tensor:
+        return self.kv_cache.buf_layer(layer_idx)
+
+    def metadata_layer(self, layer_idx: int) -> torch.Tensor:
+        return self.metadata_cache.buf_layer(layer_idx)
 
     def need_estimate(self) -> bool:
         if self.inference_page_budget is None:
@@ -200,7 +232,8 @@ class InferenceController:
 
     def invalidate_device_state(self) -> None:
         self.kv_table_full = self.meta_table_full = self.step_state = None
-        self.state_epoch += 1
+        self.kv_tables = self.meta_tables = self.step_states = None
+        self.state_epoch += 1  # graphs captured before this call are stale
 
 
 class BatchedInferenceController:
@@ -213,6 +246,8 @@ class BatchedInferenceController:
     stacks the page tables / step states and the ``*_batched`` wrappers of ``quest_amd.utils`` run every
     sequence of a decode step in one grid (grid.z = sequence); results per sequence are bit-identical to the
     single-sequence path."""
+
+    tiles_min_pages = TILES_MIN_PAGES
 
     def __init__(self, n_seqs, num_layers, num_heads, head_dim, page_size, page_budget, max_seq_len, dtype, device,
                  num_kv_heads: Optional[int] = None, layout: int = TensorLayout.NHD,
@@ -257,8 +292,6 @@ class BatchedInferenceController:
         # each stream their kv head's metadata (cfg 5: 68.9 vs 58.8 us per layer): two launches.
         self.one_launch_layers = self.num_heads == self.num_kv_heads and self._fills_the_chip(n_seqs * num_heads, device)
         self.last_layer_launches = None  # 1 / 2: which form utils.decode_layer_batched ran last (its docstring)
-        # decode_layer_batched: pools from this many pages per sequence up take the tiles launches (as InferenceController)
-        self.tiles_min_pages = getattr(self, "tiles_min_pages", 4097)
 
     @staticmethod
     def _fills_the_chip(workgroups: int, device) -> bool:
@@ -369,12 +402,7 @@ class BatchedInferenceController:
         return buf[:, :cap]
 
     def sync_device_state(self) -> None:
-        rows = []
-        for c in self.seqs:
-            kv, meta = c.kv_cache, c.metadata_cache
-            rows.append([kv.seqlen, len(kv.indicies), kv.last_page_len, kv.indicies[-1], len(meta.indicies),
-                         meta.last_page_len, meta.indicies[-1], 0])
-        self.step_states.copy_(torch.tensor(rows, dtype=torch.int32))
+        self.step_states.copy_(torch.tensor([_state_row(c) for c in self.seqs], dtype=torch.int32))
 
     def begin_graph_decode(self, dense_layers: bool = False) -> None:
         """Plan the batched sparse decode once for the configured budget (every sequence must already be in
@@ -387,15 +415,7 @@ class BatchedInferenceController:
         # what a graph captured after this call bakes in: the plan's page count and whether the launches read budgets
         self._graph_planned = budget
         self._graph_budget_ptr = self.page_budgets.data_ptr() if self.page_budgets is not None else 0
-        self._decode_handler.set_batch(self.n_seqs)
-        self._decode_handler.begin_forward(torch.tensor([0, budget - 1], dtype=torch.int32), self.num_heads,
-                                           self.num_kv_heads, self.head_dim, self.page_size, self.dtype)
-        if dense_layers:
-            if self._dense_handler is None:
-                self._dense_handler = BatchDecodeWithPagedKVCacheWrapper(kv_layout=TensorLayout.FORMAT2STR[self.layout])
-            self._dense_handler.set_batch(self.n_seqs)
-            self._dense_handler.begin_forward(torch.tensor([0, self.max_pages - 1], dtype=torch.int32), self.num_heads,
-                                              self.num_kv_heads, self.head_dim, self.page_size, self.dtype)
+        _plan_graph_handlers(self, budget, dense_layers)
 
     def clean_states(self) -> None:
         for c in self.seqs:

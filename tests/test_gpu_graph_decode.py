@@ -560,3 +560,97 @@ def test_next_tokens_reservation_riding_in_the_last_launch_equals_the_advance_la
     for l in range(layers):
         assert torch.equal(valid(sep.ctl, sep.ctl.kv_cache, L, l), valid(fold.ctl, fold.ctl.kv_cache, L, l))
         assert torch.equal(valid(sep.ctl, sep.ctl.metadata_cache, n_pages, l), valid(fold.ctl, fold.ctl.metadata_cache, n_pages, l))
+
+
+@pytest.mark.parametrize("Hq,Hkv,D,layout", [(8, 2, 128, 0)])
+def test_single_sequence_c_entries_equal_the_python_path(Hq, Hkv, D, layout):
+    """The package runs a single sequence as a batch of one through the ``_batched`` C entries; the exported ``_dyn``
+    entries (the same internal functions at ``n_seqs == 1``) stay for C callers.  Two controllers over identical pools, one
+    stepped by ``quest_amd.utils``, one by the ``_dyn`` entries called through ``quest_amd._lib.lib`` -- step advance, RoPE,
+    dense + append, append, dense, append + estimate and fused top-k (whole row and tiles) -- token after token across
+    KV-page and metadata-page boundaries: step states, page scores, outputs and pool pages identical bit for bit."""
+    import quest_amd.utils as qu
+    from quest_amd import _kernels
+    from quest_amd._lib import check, lib
+
+    dev = torch.device("cuda:0")
+    layers, B, steps = 4, 20, 45
+    L0 = 16 * 317 + 9  # 318 pages -> 321: the metadata entries move into their 21st page on the way
+    g = torch.Generator(device=dev).manual_seed(41)
+    kc = torch.randn(L0, Hkv, D, generator=g, device=dev, dtype=torch.float16)
+    vc = torch.randn(L0, Hkv, D, generator=g, device=dev, dtype=torch.float16)
+
+    def prefilled():
+        ctl = make_controller(L0, Hq, Hkv, D, PAGE, B, layout=layout, shuffle_seed=9, num_layers=layers,
+                              max_seq_len=L0 + steps + 40)
+        ctl.prepare_metadata(L0)
+        ctl.begin_forward(L0)
+        for l in range(layers):
+            qu.append_kv(kc, vc, ctl, l)
+        ctl.end_forward()
+        ctl.enable_device_state()
+        ctl.begin_graph_decode(dense_layers=True)
+        return ctl, qu.score_scratch(ctl).zero_(), qu.score_scratch(ctl).zero_()
+
+    py, c = prefilled(), prefilled()
+    assert py[0].kv_cache.full_device_table().tolist() == c[0].kv_cache.full_device_table().tolist()
+
+    def python_token(ctl, sc_row, sc_tiles, q, k, v):
+        qu.step_advance_dyn(ctl)
+        outs = [qu.decode_layer_dense_dyn(q[0], k[0], v, ctl, 0, apply_rope=True),
+                qu.decode_layer_dense_dyn(q[1], k[1], v, ctl, 1, apply_rope=True, fuse_append=False),
+                qu.decode_layer_dyn(q[2], k[2], v, ctl, 2, sc_row, apply_rope=True, tiles=False)]
+        assert ctl._decode_handler.last_launch_info()["front_end_variant"] != 8
+        outs.append(qu.decode_layer_dyn(q[3], k[3], v, ctl, 3, sc_tiles, apply_rope=True, tiles=True))
+        assert ctl._decode_handler.last_launch_info()["front_end_variant"] == 8
+        return outs
+
+    def c_token(ctl, sc_row, sc_tiles, q, k, v):
+        st, kvt, mt, s = ctl.step_state.data_ptr(), ctl.kv_table_full, ctl.meta_table_full, _kernels._stream(v)
+        sparse, dense = ctl._decode_handler._wrapper._h, ctl._dense_handler._wrapper._h
+        max_n, off = ctl.max_pages - 1, _kernels.tile_max_offset(ctl.max_pages - 1)
+        check(lib.quest_step_state_advance(st, kvt.data_ptr(), mt.data_ptr(), PAGE, kvt.numel(), mt.numel(), s), "advance")
+        outs = [torch.empty_like(q[l]) for l in range(layers)]
+        for l in range(layers):
+            check(lib.quest_apply_rope_in_place_dyn(q[l].data_ptr(), k[l].data_ptr(), Hq, Hkv, D, 1.0, 1e4, st, s), "rope")
+            kv = _kernels._paged(ctl.kv_cache.buf_layer(l), kvt, None, 1, 0, ctl.layout)
+            meta = _kernels._paged(ctl.metadata_cache.buf_layer(l), mt, None, 1, 0, ctl.layout)
+            qp, kp, vp, op = q[l].data_ptr(), k[l].data_ptr(), v.data_ptr(), outs[l].data_ptr()
+            if l == 0:
+                check(lib.quest_decode_append_forward_shared_dyn(dense, kp, vp, meta, qp, op, kv, Hq, st, None, s), "dense")
+            elif l == 1:
+                check(lib.quest_append_kv_cache_decode_dyn(kp, vp, kv, meta, st, s), "append")
+                check(lib.quest_decode_forward_shared_dyn(dense, qp, op, kv, Hq, st, None, s), "dense")
+            elif l == 2:
+                check(lib.quest_append_estimate_dyn(kp, vp, kv, qp, sc_row.data_ptr(), Hq, sc_row.size(1), max_n, meta, st, s),
+                      "estimate")
+                check(lib.quest_decode_forward_fused_topk_dyn(sparse, qp, op, kv, Hq, sc_row.data_ptr(), sc_row.size(1),
+                                                              max_n, st, None, s), "top-k")
+            else:
+                check(lib.quest_append_estimate_tiles_dyn(kp, vp, kv, qp, sc_tiles.data_ptr(), Hq, sc_tiles.size(1), max_n,
+                                                          off, meta, st, s), "estimate (tiles)")
+                check(lib.quest_decode_forward_fused_topk_tiles_dyn(sparse, qp, op, kv, Hq, sc_tiles.data_ptr(),
+                                                                    sc_tiles.size(1), max_n, off, st, None, s),
+                      "top-k (tiles)")
+        return outs
+
+    for t in range(steps):
+        q = torch.randn(layers, 1, Hq, D, generator=g, device=dev, dtype=torch.float16)
+        k = torch.randn(layers, 1, Hkv, D, generator=g, device=dev, dtype=torch.float16)
+        v = torch.randn(1, Hkv, D, generator=g, device=dev, dtype=torch.float16)
+        got = python_token(*py, q.clone(), k.clone(), v)
+        ref = c_token(*c, q.clone(), k.clone(), v)
+        for ctl, _, _ in (py, c):
+            ctl.prepare_metadata(1)
+        assert torch.equal(py[0].step_state, c[0].step_state), f"token {t}: step state"
+        n = len(py[0].kv_cache.indicies) - 1
+        assert torch.equal(py[1][:, :n], c[1][:, :n]) and torch.equal(py[2][:, :n], c[2][:, :n]), f"token {t}: scores"
+        for l in range(layers):
+            assert torch.equal(got[l], ref[l]), f"token {t} layer {l}: outputs"
+    assert len(py[0].metadata_cache.indicies) == 21 and py[0].kv_cache.indicies == c[0].kv_cache.indicies
+    full_kv = torch.tensor(py[0].kv_cache.indicies[:-1], device=dev)
+    full_meta = torch.tensor(py[0].metadata_cache.indicies[:-1], device=dev)
+    for l in range(layers):
+        assert torch.equal(py[0].kv_cache.buf_layer(l)[full_kv], c[0].kv_cache.buf_layer(l)[full_kv]), f"layer {l}: KV pool"
+        assert torch.equal(py[0].metadata_cache.buf_layer(l)[full_meta], c[0].metadata_cache.buf_layer(l)[full_meta]), \
+            f"layer {l}: metadata pool"

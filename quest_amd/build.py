@@ -82,6 +82,47 @@ def build(force: bool = False, verbose: bool = False) -> str:
     return LIB
 
 
+def _code_objects(lib_path: str, d: str):
+    """The gfx950 code objects of a built library (one per source file), unbundled into directory `d`."""
+    import re
+
+    llvm = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
+    fat = os.path.join(d, "fat.bin")  # one offload bundle per source file, concatenated in .hip_fatbin
+    subprocess.check_call([f"{llvm}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat])
+    blob = open(fat, "rb").read()
+    starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), blob)]
+    out = []
+    for i, st in enumerate(starts):
+        part, co = os.path.join(d, f"b{i}.bin"), os.path.join(d, f"k{i}.co")
+        open(part, "wb").write(blob[st:(starts[i + 1] if i + 1 < len(starts) else len(blob))])
+        subprocess.check_call([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={part}",
+                               "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
+        out.append(co)
+    return out
+
+
+def kernel_code_hashes(lib_path: str = LIB):
+    """{mangled name: (code bytes, sha256 of the function's machine code)} of every function in the library's gfx950 code
+    objects: two builds whose tables are equal run the same device code (scripts/kernel_meta.py --same-code)."""
+    import hashlib
+    import tempfile
+
+    llvm = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        for co in _code_objects(lib_path, d):
+            blob = open(co, "rb").read()
+            text = [ln.replace("[", " ").replace("]", " ").split() for ln in
+                    subprocess.check_output([f"{llvm}/llvm-readelf", "-SW", co], text=True).splitlines() if " .text " in ln][0]
+            addr, off = int(text[3], 16), int(text[4], 16)  # [nr] .text PROGBITS address offset size
+            for ln in subprocess.check_output([f"{llvm}/llvm-readelf", "-sW", co], text=True).splitlines():
+                f = ln.split()
+                if len(f) >= 8 and f[3] == "FUNC":
+                    start, size = int(f[1], 16) - addr + off, int(f[2])
+                    out[f[7]] = (size, hashlib.sha256(blob[start:start + size]).hexdigest())
+    return out
+
+
 def kernel_metadata(lib_path: str = LIB):
     """Code-object metadata of every kernel in the built library: {mangled name: {vgpr, vgpr_spill, scratch, lds, sgpr,
     code_bytes}} (clang-offload-bundler + llvm-readelf from the ROCm LLVM; no GPU needed).  Used by
@@ -92,15 +133,7 @@ def kernel_metadata(lib_path: str = LIB):
     llvm = os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
     notes, syms = "", ""
     with tempfile.TemporaryDirectory() as d:
-        fat = os.path.join(d, "fat.bin")  # one offload bundle per source file, concatenated in .hip_fatbin
-        subprocess.check_call([f"{llvm}/llvm-objcopy", "-O", "binary", "--only-section=.hip_fatbin", lib_path, fat])
-        blob = open(fat, "rb").read()
-        starts = [m.start() for m in re.finditer(re.escape(b"__CLANG_OFFLOAD_BUNDLE__"), blob)]
-        for i, st in enumerate(starts):
-            part, co = os.path.join(d, f"b{i}.bin"), os.path.join(d, f"k{i}.co")
-            open(part, "wb").write(blob[st:(starts[i + 1] if i + 1 < len(starts) else len(blob))])
-            subprocess.check_call([f"{llvm}/clang-offload-bundler", "--unbundle", "--type=o", f"--input={part}",
-                                   "--targets=hipv4-amdgcn-amd-amdhsa--gfx950", f"--output={co}"])
+        for co in _code_objects(lib_path, d):
             notes += subprocess.check_output([f"{llvm}/llvm-readelf", "--notes", co], text=True)
             syms += subprocess.check_output([f"{llvm}/llvm-readelf", "-sW", co], text=True)
     size = {}

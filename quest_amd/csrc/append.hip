@@ -9,6 +9,7 @@
 // gfx950 mapping: one row of D/8 lanes owns one (page, head) vector, 16 B per lane, so a wave
 // moves 4 heads x 256 B = 1 KiB contiguous (NHD) per instruction.  Bound: HBM (pure copy + RMW).
 #include "append_device.cuh"
+#include "pool_check.h"
 
 namespace quest {
 
@@ -123,34 +124,36 @@ int check_pool(const quest_paged_kv_t& p) {
 
 using namespace quest;
 
-extern "C" int quest_append_kv_cache_decode(const void* k, const void* v, quest_paged_kv_t kv,
-                                            quest_paged_kv_t metadata, quest_stream_t stream) {
-    if (!k || !v) return QUEST_EINVAL;
-    if (int e = check_pool(kv)) return e;
-    if (int e = check_pool(metadata)) return e;
-    if (kv.num_heads != metadata.num_heads || kv.head_dim != metadata.head_dim) return QUEST_EINVAL;
+// one token per sequence into the pools; a state-driven launch (`state` != NULL) reads lengths / last pages per sequence
+static int append_decode(const void* k, const void* v, quest_paged_kv_t kv, quest_paged_kv_t metadata,
+                         const quest_step_state_t* state, uint32_t n_seqs, quest_stream_t stream) {
+    if (!k || !v || n_seqs == 0) return QUEST_EINVAL;
+    if (int e = check_pool_pair(kv, metadata, state != nullptr, false)) return e;
     const uint32_t threads = kv.num_heads * (kv.head_dim / kVec);
     const uint32_t block = 256, grid = (threads + block - 1) / block;
-    hipLaunchKernelGGL(append_decode_kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, kv, metadata,
-                       (const uint16_t*)k, (const uint16_t*)v, (const quest_step_state_t*)nullptr);
+    hipLaunchKernelGGL(append_decode_kernel, dim3(grid, n_seqs), dim3(block), 0, (hipStream_t)stream, kv, metadata,
+                       (const uint16_t*)k, (const uint16_t*)v, state);
     QUEST_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int quest_append_kv_cache_decode(const void* k, const void* v, quest_paged_kv_t kv,
+                                            quest_paged_kv_t metadata, quest_stream_t stream) {
+    return append_decode(k, v, kv, metadata, nullptr, 1, stream);
 }
 
 extern "C" int quest_append_kv_cache_decode_dyn(const void* k, const void* v, quest_paged_kv_t kv,
                                                 quest_paged_kv_t metadata, const quest_step_state_t* state,
                                                 quest_stream_t stream) {
-    if (!k || !v || !state) return QUEST_EINVAL;
-    kv.last_page_len = metadata.last_page_len = 1;  // placeholders; the kernel reads the real ones from `state`
-    if (int e = check_pool(kv)) return e;
-    if (int e = check_pool(metadata)) return e;
-    if (kv.num_heads != metadata.num_heads || kv.head_dim != metadata.head_dim) return QUEST_EINVAL;
-    const uint32_t threads = kv.num_heads * (kv.head_dim / kVec);
-    const uint32_t block = 256, grid = (threads + block - 1) / block;
-    hipLaunchKernelGGL(append_decode_kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, kv, metadata,
-                       (const uint16_t*)k, (const uint16_t*)v, state);
-    QUEST_LAUNCH_CHECK();
-    return 0;
+    if (!state) return QUEST_EINVAL;
+    return append_decode(k, v, kv, metadata, state, 1, stream);
+}
+
+extern "C" int quest_append_kv_cache_decode_batched(const void* k, const void* v, quest_paged_kv_t kv,
+                                                    quest_paged_kv_t metadata, const quest_step_state_t* state,
+                                                    quest_batch_t batch, quest_stream_t stream) {
+    if (!state) return QUEST_EINVAL;
+    return append_decode(k, v, kv, metadata, state, batch.n_seqs, stream);
 }
 
 extern "C" int quest_append_kv_cache_prefill(const void* k, const void* v, uint32_t append_len,
@@ -158,9 +161,7 @@ extern "C" int quest_append_kv_cache_prefill(const void* k, const void* v, uint3
                                              quest_paged_kv_t metadata, quest_stream_t stream) {
     if (!k || !v || append_len == 0 || n_pages_host == 0) return QUEST_EINVAL;
     if (!kv.indptr || !metadata.indptr) return QUEST_EINVAL;
-    if (int e = check_pool(kv)) return e;
-    if (int e = check_pool(metadata)) return e;
-    if (kv.num_heads != metadata.num_heads || kv.head_dim != metadata.head_dim) return QUEST_EINVAL;
+    if (int e = check_pool_pair(kv, metadata, false, false)) return e;
     // pages touched: from the page holding the first appended token to the last page
     const uint64_t seq_len = (uint64_t)(n_pages_host - 1) * kv.page_size + kv.last_page_len;
     if (append_len > seq_len) return QUEST_EINVAL;
@@ -176,23 +177,9 @@ extern "C" int quest_append_kv_cache_prefill(const void* k, const void* v, uint3
     return 0;
 }
 
-extern "C" int quest_step_state_advance(quest_step_state_t* state, const int32_t* kv_table, const int32_t* meta_table,
-                                        uint32_t page_size, uint32_t max_kv_pages, uint32_t max_meta_pages,
-                                        quest_stream_t stream) {
-    if (!state || !kv_table || !meta_table || page_size == 0 || max_kv_pages == 0 || max_meta_pages == 0) return QUEST_EINVAL;
-    const quest_batch_t one = {1, 0, 0, 0};
-    hipLaunchKernelGGL(step_state_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, state, kv_table, meta_table,
-                       page_size, max_kv_pages, max_meta_pages, one);
-    QUEST_LAUNCH_CHECK();
-    return 0;
-}
-
-extern "C" int quest_step_state_advance_batched(quest_step_state_t* state, const int32_t* kv_tables,
-                                                const int32_t* meta_tables, uint32_t page_size, uint32_t max_kv_pages,
-                                                uint32_t max_meta_pages, quest_batch_t batch, quest_stream_t stream) {
+static int step_state_advance(quest_step_state_t* state, const int32_t* kv_tables, const int32_t* meta_tables, uint32_t page_size,
+                              uint32_t max_kv_pages, uint32_t max_meta_pages, quest_batch_t batch, quest_stream_t stream) {
     if (!state || !kv_tables || !meta_tables || page_size == 0 || max_kv_pages == 0 || max_meta_pages == 0)
-        return QUEST_EINVAL;
-    if (batch.n_seqs == 0 || batch.kv_table_stride < max_kv_pages || batch.meta_table_stride < max_meta_pages)
         return QUEST_EINVAL;
     hipLaunchKernelGGL(step_state_advance_kernel, dim3((batch.n_seqs + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        state, kv_tables, meta_tables, page_size, max_kv_pages, max_meta_pages, batch);
@@ -200,18 +187,16 @@ extern "C" int quest_step_state_advance_batched(quest_step_state_t* state, const
     return 0;
 }
 
-extern "C" int quest_append_kv_cache_decode_batched(const void* k, const void* v, quest_paged_kv_t kv,
-                                                    quest_paged_kv_t metadata, const quest_step_state_t* state,
-                                                    quest_batch_t batch, quest_stream_t stream) {
-    if (!k || !v || !state || batch.n_seqs == 0) return QUEST_EINVAL;
-    kv.last_page_len = metadata.last_page_len = 1;  // placeholders; the kernel reads the real ones from `state`
-    if (int e = check_pool(kv)) return e;
-    if (int e = check_pool(metadata)) return e;
-    if (kv.num_heads != metadata.num_heads || kv.head_dim != metadata.head_dim) return QUEST_EINVAL;
-    const uint32_t threads = kv.num_heads * (kv.head_dim / kVec);
-    const uint32_t block = 256, grid = (threads + block - 1) / block;
-    hipLaunchKernelGGL(append_decode_kernel, dim3(grid, batch.n_seqs), dim3(block), 0, (hipStream_t)stream, kv, metadata,
-                       (const uint16_t*)k, (const uint16_t*)v, state);
-    QUEST_LAUNCH_CHECK();
-    return 0;
+extern "C" int quest_step_state_advance(quest_step_state_t* state, const int32_t* kv_table, const int32_t* meta_table,
+                                        uint32_t page_size, uint32_t max_kv_pages, uint32_t max_meta_pages,
+                                        quest_stream_t stream) {
+    return step_state_advance(state, kv_table, meta_table, page_size, max_kv_pages, max_meta_pages, {1, 0, 0, 0}, stream);
+}
+
+extern "C" int quest_step_state_advance_batched(quest_step_state_t* state, const int32_t* kv_tables,
+                                                const int32_t* meta_tables, uint32_t page_size, uint32_t max_kv_pages,
+                                                uint32_t max_meta_pages, quest_batch_t batch, quest_stream_t stream) {
+    if (batch.n_seqs == 0 || batch.kv_table_stride < max_kv_pages || batch.meta_table_stride < max_meta_pages)
+        return QUEST_EINVAL;
+    return step_state_advance(state, kv_tables, meta_tables, page_size, max_kv_pages, max_meta_pages, batch, stream);
 }

@@ -1,5 +1,5 @@
 // Device code of the sparse paged decode attention: kernel parameters, the online-softmax row state, the merge of the
-// per-workgroup partial states (merge_states_kernel's fast path) and the workgroup body of sparse_decode_kernel (sparse_attn.hip, which also holds the reference citations and the design notes).
+// per-workgroup partial states (merge_states_kernel's fast path) and the workgroup body of sparse_decode_kernel (the kernels: decode_kernels.cuh; reference citations, design notes, planner and launchers: sparse_attn.hip).
 #pragma once
 #include "estimate_device.cuh"
 #include "stamps.cuh"

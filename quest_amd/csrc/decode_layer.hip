@@ -862,6 +862,9 @@ static bool plan_persist(const SkinnyArgs& a, uint32_t virtual_rows, uint32_t tg
     return true;
 }
 
+// groups of 4 tokens a workgroup of the n-token kernels carries: the TG instantiation
+static uint32_t token_groups(uint32_t n_tokens) { return n_tokens <= 4 ? 1 : (n_tokens <= 8 ? 2 : 4); }
+
 // QUEST_BATCHED_GEMV=skinny forces the first kernel (tuning / tests).
 template <int MODE>
 static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_t s) {
@@ -871,7 +874,7 @@ static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_
         const char* e = quest_tuning_env("QUEST_BATCHED_GEMV");
         return e && e[0] == 's';
     }();
-    const uint32_t tg = a.n_tokens <= 4 ? 1 : (a.n_tokens <= 8 ? 2 : 4);
+    const uint32_t tg = token_groups(a.n_tokens);
     PersistPlan pl{};
     uint32_t grid = 0;
     size_t lds = 0;
@@ -888,56 +891,81 @@ static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_
 
 using namespace quest;
 
+// ---- GemvArgs of the four launches, as the single-token and the n-token entries both fill them
+static GemvArgs plain_args(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim, uint32_t out_dim) {
+    GemvArgs p{};
+    p.x = (const half_t*)x, p.gamma = (const half_t*)gamma, p.eps = eps, p.in_dim = in_dim;
+    p.w[0] = (const half_t*)w, p.rows[0] = out_dim, p.out[0] = (half_t*)out;
+    return p;
+}
+static GemvArgs residual_args(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim) {
+    GemvArgs p = plain_args(x, nullptr, 0.f, w, h, in_dim, out_dim);
+    p.residual = (const half_t*)h;
+    return p;
+}
+static GemvArgs gate_up_args(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up, void* act,
+                             uint32_t hidden, uint32_t intermediate) {
+    GemvArgs p = plain_args(h, gamma, eps, w_gate, act, hidden, intermediate);
+    p.w[1] = (const half_t*)w_up, p.rows[1] = intermediate;
+    return p;
+}
+// n-token form of a launch: contiguous rows of inputs and of the (first) output
+static SkinnyArgs skinny_args(const GemvArgs& g, uint32_t n_tokens) {
+    SkinnyArgs a{};
+    a.g = g;
+    a.n_tokens = n_tokens, a.x_stride = g.in_dim, a.out_stride[0] = g.rows[0];
+    return a;
+}
+
 extern "C" int quest_decode_norm_gemv(const void* x, const void* gamma, float eps, const void* w, void* out,
                                       uint32_t in_dim, uint32_t out_dim, quest_stream_t stream) {
     if (!x || !w || !out || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
     if (in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
-    GemvArgs p{};
-    p.x = (const half_t*)x, p.gamma = (const half_t*)gamma, p.eps = eps, p.in_dim = in_dim;
-    p.w[0] = (const half_t*)w, p.rows[0] = out_dim, p.out[0] = (half_t*)out;
-    return launch_gemv<kGvPlain>(p, out_dim, (hipStream_t)stream);
+    return launch_gemv<kGvPlain>(plain_args(x, gamma, eps, w, out, in_dim, out_dim), out_dim, (hipStream_t)stream);
 }
 
 extern "C" int quest_decode_gemv_residual(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
                                           quest_stream_t stream) {
     if (!x || !w || !h || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
     if (in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
-    GemvArgs p{};
-    p.x = (const half_t*)x, p.in_dim = in_dim;
-    p.w[0] = (const half_t*)w, p.rows[0] = out_dim, p.out[0] = (half_t*)h, p.residual = (const half_t*)h;
-    return launch_gemv<kGvResidual>(p, out_dim, (hipStream_t)stream);
+    return launch_gemv<kGvResidual>(residual_args(x, w, h, in_dim, out_dim), out_dim, (hipStream_t)stream);
 }
 
 extern "C" int quest_decode_mlp_gate_up(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
                                         void* act, uint32_t hidden, uint32_t intermediate, quest_stream_t stream) {
     if (!h || !gamma || !w_gate || !w_up || !act || hidden == 0 || intermediate == 0) return QUEST_EINVAL;
     if (hidden % 8 != 0) return QUEST_EUNSUPPORTED;
-    GemvArgs p{};
-    p.x = (const half_t*)h, p.gamma = (const half_t*)gamma, p.eps = eps, p.in_dim = hidden;
-    p.w[0] = (const half_t*)w_gate, p.w[1] = (const half_t*)w_up, p.rows[0] = p.rows[1] = intermediate;
-    p.out[0] = (half_t*)act;
-    return launch_gemv<kGvSiluMul>(p, 2 * intermediate, (hipStream_t)stream);
+    return launch_gemv<kGvSiluMul>(gate_up_args(h, gamma, eps, w_gate, w_up, act, hidden, intermediate), 2 * intermediate,
+                                   (hipStream_t)stream);
 }
 
+struct RopeArgs {  // rotation of the q-k-v launch: closed form (inv_freq NULL) or a frequency table
+    float rcp_scale, log2_rcp_theta;
+    const float* inv_freq;
+    float attn_factor;
+};
+
+// batched: the n-token launch (one state per token), else the single-token one (`states` = the one state)
 static int qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
                     void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
-                    float rcp_scale, float log2_rcp_theta, const float* inv_freq, float attn_factor,
-                    const quest_step_state_t* state, quest_stream_t stream) {
-    if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v || !state) return QUEST_EINVAL;
+                    RopeArgs rope, const quest_step_state_t* states, bool batched, uint32_t n_tokens, quest_stream_t stream) {
+    if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v || !states) return QUEST_EINVAL;
     if (hidden == 0 || num_qo_heads == 0 || num_kv_heads == 0) return QUEST_EINVAL;
-    if (hidden % 8 != 0 || head_dim % 4 != 0) return QUEST_EUNSUPPORTED;  // a wave's 4 row-dots = two rotation pairs of one head
-    GemvArgs p{};
-    p.x = (const half_t*)h, p.gamma = (const half_t*)gamma, p.eps = eps, p.in_dim = hidden;
-    p.w[0] = (const half_t*)wq, p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
-    p.rows[0] = num_qo_heads * head_dim, p.rows[1] = p.rows[2] = num_kv_heads * head_dim;
-    p.out[0] = (half_t*)q, p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
-    p.head_dim = head_dim, p.rcp_scale = rcp_scale, p.log2_rcp_theta = log2_rcp_theta, p.state = state;
-    p.inv_freq = inv_freq, p.attn_factor = attn_factor;
-    return launch_gemv<kGvQkvRope>(p, p.rows[0] + p.rows[1] + p.rows[2], (hipStream_t)stream);
-}
-
-static bool bad_rope_table(const float* inv_freq, float attention_factor) {
-    return !inv_freq || !(attention_factor > 0.f) || !std::isfinite(attention_factor);
+    // one token: a wave's 4 row-dots = two rotation pairs of one head; n tokens: a 16-row block = 8 rotation pairs of ONE
+    // head of ONE matrix
+    if (batched ? head_dim % 16 != 0 : (hidden % 8 != 0 || head_dim % 4 != 0)) return QUEST_EUNSUPPORTED;
+    GemvArgs p = plain_args(h, gamma, eps, wq, q, hidden, num_qo_heads * head_dim);
+    p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
+    p.rows[1] = p.rows[2] = num_kv_heads * head_dim;
+    p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
+    p.head_dim = head_dim, p.rcp_scale = rope.rcp_scale, p.log2_rcp_theta = rope.log2_rcp_theta, p.state = states;
+    p.inv_freq = rope.inv_freq, p.attn_factor = rope.attn_factor;
+    const uint32_t rows = p.rows[0] + p.rows[1] + p.rows[2];
+    if (!batched) return launch_gemv<kGvQkvRope>(p, rows, (hipStream_t)stream);
+    SkinnyArgs a = skinny_args(p, n_tokens);
+    a.out_stride[1] = p.rows[1], a.out_stride[2] = p.rows[2];
+    a.state_stride = 1;
+    return launch_batched<kGvQkvRope>(a, rows, (hipStream_t)stream);
 }
 
 extern "C" int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
@@ -945,8 +973,8 @@ extern "C" int quest_decode_qkv_rope(const void* h, const void* gamma, float eps
                                      uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
                                      const quest_step_state_t* state, quest_stream_t stream) {
     if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
-    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, 1.0f / rope_scale,
-                    -log2f(rope_theta), nullptr, 1.0f, state, stream);
+    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
+                    {1.0f / rope_scale, -log2f(rope_theta), nullptr, 1.0f}, state, false, 0, stream);
 }
 
 extern "C" int quest_decode_qkv_rope_freqs(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
@@ -955,32 +983,24 @@ extern "C" int quest_decode_qkv_rope_freqs(const void* h, const void* gamma, flo
                                            const float* inv_freq, float attention_factor,
                                            const quest_step_state_t* state, quest_stream_t stream) {
     if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
-    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, 1.0f, 0.f, inv_freq,
-                    attention_factor, state, stream);
+    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
+                    {1.0f, 0.f, inv_freq, attention_factor}, state, false, 0, stream);
 }
 
 // ---- the same for n_tokens <= 16 decode tokens (x: [n_tokens][in_dim], outputs [n_tokens][out_dim], contiguous)
 extern "C" int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out,
                                               uint32_t in_dim, uint32_t out_dim, uint32_t n_tokens, quest_stream_t stream) {
     if (!x || !w || !out || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
-    SkinnyArgs a{};
-    GemvArgs& p = a.g;
-    p.x = (const half_t*)x, p.gamma = (const half_t*)gamma, p.eps = eps, p.in_dim = in_dim;
-    p.w[0] = (const half_t*)w, p.rows[0] = out_dim, p.out[0] = (half_t*)out;
-    a.n_tokens = n_tokens, a.x_stride = in_dim, a.out_stride[0] = out_dim;
-    return launch_batched<kGvPlain>(a, out_dim, (hipStream_t)stream);
+    return launch_batched<kGvPlain>(skinny_args(plain_args(x, gamma, eps, w, out, in_dim, out_dim), n_tokens), out_dim,
+                                    (hipStream_t)stream);
 }
 
 extern "C" int quest_decode_gemv_residual_batched(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
                                                   uint32_t n_tokens, quest_stream_t stream) {
     if (!x || !w || !h || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
-    SkinnyArgs a{};
-    GemvArgs& p = a.g;
-    p.x = (const half_t*)x, p.in_dim = in_dim;
-    p.w[0] = (const half_t*)w, p.rows[0] = out_dim, p.out[0] = (half_t*)h, p.residual = (const half_t*)h;
-    a.n_tokens = n_tokens, a.x_stride = in_dim, a.out_stride[0] = out_dim;
+    SkinnyArgs a = skinny_args(residual_args(x, w, h, in_dim, out_dim), n_tokens);
 #ifdef QUEST_PS_TIMELINE
-    if (const char* e = quest_tuning_env("QUEST_PS_DEBUG_PTR")) p.out[2] = reinterpret_cast<half_t*>(strtoull(e, nullptr, 0));
+    if (const char* e = quest_tuning_env("QUEST_PS_DEBUG_PTR")) a.g.out[2] = reinterpret_cast<half_t*>(strtoull(e, nullptr, 0));
 #endif
     return launch_batched<kGvResidual>(a, out_dim, (hipStream_t)stream);
 }
@@ -989,34 +1009,8 @@ extern "C" int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma
                                                 const void* w_up, void* act, uint32_t hidden, uint32_t intermediate,
                                                 uint32_t n_tokens, quest_stream_t stream) {
     if (!h || !gamma || !w_gate || !w_up || !act || hidden == 0 || intermediate == 0) return QUEST_EINVAL;
-    SkinnyArgs a{};
-    GemvArgs& p = a.g;
-    p.x = (const half_t*)h, p.gamma = (const half_t*)gamma, p.eps = eps, p.in_dim = hidden;
-    p.w[0] = (const half_t*)w_gate, p.w[1] = (const half_t*)w_up, p.rows[0] = p.rows[1] = intermediate;
-    p.out[0] = (half_t*)act;
-    a.n_tokens = n_tokens, a.x_stride = hidden, a.out_stride[0] = intermediate;
+    SkinnyArgs a = skinny_args(gate_up_args(h, gamma, eps, w_gate, w_up, act, hidden, intermediate), n_tokens);
     return launch_batched<kGvSiluMul>(a, 2 * intermediate, (hipStream_t)stream);
-}
-
-static int qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
-                            void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                            uint32_t head_dim, float rcp_scale, float log2_rcp_theta, const float* inv_freq,
-                            float attn_factor, const quest_step_state_t* states, uint32_t n_tokens, quest_stream_t stream) {
-    if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v || !states) return QUEST_EINVAL;
-    if (hidden == 0 || num_qo_heads == 0 || num_kv_heads == 0) return QUEST_EINVAL;
-    if (head_dim % 16 != 0) return QUEST_EUNSUPPORTED;  // a 16-row block = 8 rotation pairs of ONE head of ONE matrix
-    SkinnyArgs a{};
-    GemvArgs& p = a.g;
-    p.x = (const half_t*)h, p.gamma = (const half_t*)gamma, p.eps = eps, p.in_dim = hidden;
-    p.w[0] = (const half_t*)wq, p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
-    p.rows[0] = num_qo_heads * head_dim, p.rows[1] = p.rows[2] = num_kv_heads * head_dim;
-    p.out[0] = (half_t*)q, p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
-    p.head_dim = head_dim, p.rcp_scale = rcp_scale, p.log2_rcp_theta = log2_rcp_theta, p.state = states;
-    p.inv_freq = inv_freq, p.attn_factor = attn_factor;
-    a.n_tokens = n_tokens, a.x_stride = hidden;
-    a.out_stride[0] = p.rows[0], a.out_stride[1] = p.rows[1], a.out_stride[2] = p.rows[2];
-    a.state_stride = 1;
-    return launch_batched<kGvQkvRope>(a, p.rows[0] + p.rows[1] + p.rows[2], (hipStream_t)stream);
 }
 
 extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
@@ -1025,8 +1019,8 @@ extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, f
                                              float rope_scale, float rope_theta, const quest_step_state_t* states,
                                              uint32_t n_tokens, quest_stream_t stream) {
     if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
-    return qkv_rope_batched(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
-                            1.0f / rope_scale, -log2f(rope_theta), nullptr, 1.0f, states, n_tokens, stream);
+    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
+                    {1.0f / rope_scale, -log2f(rope_theta), nullptr, 1.0f}, states, true, n_tokens, stream);
 }
 
 extern "C" int quest_decode_qkv_rope_batched_freqs(const void* h, const void* gamma, float eps, const void* wq,
@@ -1036,8 +1030,8 @@ extern "C" int quest_decode_qkv_rope_batched_freqs(const void* h, const void* ga
                                                    const quest_step_state_t* states, uint32_t n_tokens,
                                                    quest_stream_t stream) {
     if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
-    return qkv_rope_batched(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, 1.0f, 0.f,
-                            inv_freq, attention_factor, states, n_tokens, stream);
+    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
+                    {1.0f, 0.f, inv_freq, attention_factor}, states, true, n_tokens, stream);
 }
 
 // Which kernel an n-token launch of this shape takes (tests / tuning; no launch): returns 1 and fills
@@ -1048,7 +1042,7 @@ extern "C" int quest_decode_batched_plan(uint32_t in_dim, uint32_t virtual_rows,
     if (in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
     SkinnyArgs a{};
     a.g.in_dim = in_dim, a.n_tokens = n_tokens;
-    const uint32_t tg = n_tokens <= 4 ? 1 : (n_tokens <= 8 ? 2 : 4);
+    const uint32_t tg = token_groups(n_tokens);
     PersistPlan pl{};
     uint32_t grid = 0;
     size_t lds = 0;

@@ -19,6 +19,7 @@
 // MHA and 2.3 us at GQA-4 here), lane 0's value is cast once to fp16 (RNE).  The oracle (qo_estimate)
 // restates exactly this tree, so HIP == oracle bit for bit.  Bound: HBM.
 #include "estimate_device.cuh"
+#include "pool_check.h"
 
 namespace quest {
 
@@ -147,12 +148,8 @@ static int dispatch_group(uint32_t G, const void* q, void* o, uint32_t n_out, co
 
 using namespace quest;
 
-namespace quest {
-int check_pool(const quest_paged_kv_t& p);  // append.hip
-}
-
 static int estimate_entry(const void* q, void* o, uint32_t num_qo_heads, uint32_t n_out, const quest_paged_kv_t& metadata,
-                          const AppendTail& tail, hipStream_t s, uint32_t n_seqs = 1) {
+                          const AppendTail& tail, hipStream_t s, uint32_t n_seqs) {
     if (!q || !metadata.data || !metadata.indices) return QUEST_EINVAL;
     if (metadata.layout > QUEST_LAYOUT_NHD_ROT || metadata.num_heads == 0 || metadata.page_size == 0) return QUEST_EINVAL;
     if (num_qo_heads == 0 || num_qo_heads % metadata.num_heads != 0) return QUEST_EINVAL;
@@ -170,28 +167,28 @@ static int estimate_entry(const void* q, void* o, uint32_t num_qo_heads, uint32_
 extern "C" int quest_estimate_attn_score(const void* q, void* o, uint32_t num_qo_heads, uint32_t n_out,
                                          quest_paged_kv_t metadata, quest_stream_t stream) {
     AppendTail tail{};
-    return estimate_entry(q, o, num_qo_heads, n_out, metadata, tail, (hipStream_t)stream);
+    return estimate_entry(q, o, num_qo_heads, n_out, metadata, tail, (hipStream_t)stream, 1);
+}
+
+// the append role of an estimate launch: this token's K / V into `kv` (the blocks behind the estimate's)
+static AppendTail append_tail(const void* k, const void* v, const quest_paged_kv_t& kv, uint32_t o_stride) {
+    AppendTail tail{};
+    tail.kv = kv, tail.key = (const uint16_t*)k, tail.value = (const uint16_t*)v;
+    tail.enabled = 1, tail.o_stride = o_stride;
+    return tail;
 }
 
 static int append_estimate_state(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
                                  uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
                                  quest_paged_kv_t metadata, const quest_step_state_t* state, quest_batch_t batch,
-                                 quest_stream_t stream, uint32_t tile_off = 0) {
+                                 quest_stream_t stream, uint32_t tile_off) {
     if (!k || !v || !state || max_n_out == 0 || o_stride < max_n_out || batch.n_seqs == 0) return QUEST_EINVAL;
     if (tile_off && (tile_off % 8u != 0 || tile_off < ((max_n_out + 7u) & ~7u) ||
                      o_stride < tile_off + ((((max_n_out + 7u) / 8u) + 3u) & ~3u)))
         return QUEST_EINVAL;  // the maxima live behind the scores of the same row, readable in 8-byte pieces
-    kv.last_page_len = metadata.last_page_len = 1;  // placeholders; the kernel reads the real ones from `state`
-    if (int e = check_pool(kv)) return e;
-    if (int e = check_pool(metadata)) return e;
-    if (kv.num_heads != metadata.num_heads || kv.head_dim != metadata.head_dim) return QUEST_EINVAL;
-    AppendTail tail{};
-    tail.kv = kv;
-    tail.key = (const uint16_t*)k;
-    tail.value = (const uint16_t*)v;
-    tail.enabled = 1;
+    if (int e = check_pool_pair(kv, metadata, true, false)) return e;
+    AppendTail tail = append_tail(k, v, kv, o_stride);
     tail.state = state;
-    tail.o_stride = o_stride;
     tail.meta_table_stride = batch.meta_table_stride;
     tail.tile_off = tile_off;
     return estimate_entry(q, o, num_qo_heads, max_n_out, metadata, tail, (hipStream_t)stream, batch.n_seqs);
@@ -216,7 +213,7 @@ extern "C" int quest_append_estimate_dyn(const void* k, const void* v, quest_pag
                                          quest_paged_kv_t metadata, const quest_step_state_t* state,
                                          quest_stream_t stream) {
     const quest_batch_t one = {1, 0, 0, 0};
-    return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, one, stream);
+    return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, one, stream, 0);
 }
 
 extern "C" int quest_append_estimate_tiles_dyn(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
@@ -235,7 +232,7 @@ extern "C" int quest_append_estimate_batched(const void* k, const void* v, quest
                                              quest_batch_t batch, quest_stream_t stream) {
     // every sequence's metadata table must cover the entries the grid is sized for
     if (batch.n_seqs > 1 && (uint64_t)batch.meta_table_stride * metadata.page_size < max_n_out) return QUEST_EINVAL;
-    return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, batch, stream);
+    return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, batch, stream, 0);
 }
 
 // The batched twin of quest_append_estimate_tiles_dyn: every row of `o` ([n_seqs][num_qo_heads][o_stride]) carries its own
@@ -259,16 +256,9 @@ extern "C" int quest_append_estimate_strided(const void* k, const void* v, quest
                                              uint32_t num_qo_heads, uint32_t n_out, uint32_t o_stride,
                                              quest_paged_kv_t metadata, quest_stream_t stream) {
     if (!k || !v || (o_stride != 0 && o_stride < n_out)) return QUEST_EINVAL;
-    if (int e = check_pool(kv)) return e;
-    if (int e = check_pool(metadata)) return e;
-    if (kv.num_heads != metadata.num_heads || kv.head_dim != metadata.head_dim) return QUEST_EINVAL;
-    AppendTail tail{};
-    tail.kv = kv;
-    tail.key = (const uint16_t*)k;
-    tail.value = (const uint16_t*)v;
-    tail.enabled = 1;
-    tail.o_stride = o_stride;
-    return estimate_entry(q, o, num_qo_heads, n_out, metadata, tail, (hipStream_t)stream);
+    if (int e = check_pool_pair(kv, metadata, false, false)) return e;
+    AppendTail tail = append_tail(k, v, kv, o_stride);
+    return estimate_entry(q, o, num_qo_heads, n_out, metadata, tail, (hipStream_t)stream, 1);
 }
 
 extern "C" int quest_append_estimate(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,

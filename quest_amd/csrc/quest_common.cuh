@@ -280,6 +280,18 @@ static inline const char* quest_tuning_env(const char* name) {
     static const bool on = [] { const char* e = getenv("QUEST_TUNING"); return e && atoi(e) != 0; }();
     return on ? getenv(name) : nullptr;
 }
+// an integer knob: its value, `unset` when it is not set (or tuning is off).  Callers that read a knob once per process
+// keep it in a function-local static.
+static inline int quest_tuning_int(const char* name, int unset) {
+    const char* e = quest_tuning_env(name);
+    return e ? atoi(e) : unset;
+}
+
+// a frequency-table rotation (the *_freqs entries) that cannot be used: no table, or a factor that is not a positive number
+#include <cmath>
+static inline bool bad_rope_table(const float* inv_freq, float attention_factor) {
+    return !inv_freq || !(attention_factor > 0.f) || !std::isfinite(attention_factor);
+}
 
 #define QUEST_LAUNCH_CHECK()                  \
     do {                                      \

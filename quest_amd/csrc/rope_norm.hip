@@ -142,7 +142,7 @@ extern "C" int quest_apply_rope_in_place_freqs(void* q, void* k, uint32_t n, uin
                                                uint32_t num_kv_heads, uint32_t head_dim, const float* inv_freq,
                                                float attention_factor, const quest_step_state_t* states,
                                                quest_stream_t stream) {
-    if (!inv_freq || !(attention_factor > 0.f) || !std::isfinite(attention_factor)) return QUEST_EINVAL;
+    if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
     return rope_launch(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, 1.0f, 0.f, inv_freq, attention_factor,
                        states, stream);
 }

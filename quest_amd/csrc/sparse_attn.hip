@@ -23,381 +23,10 @@
 #include <new>
 #include <vector>
 
-#include "append_device.cuh"
-#include "decode_device.cuh"
-#include "layer_device.cuh"
-
-namespace quest {
-
-// Workgroups go to the 8 XCDs round-robin by linear workgroup id, and each XCD has its own L2.  With GQA the query
-// heads of a kv-head group select overlapping page sets (measured: 21 % of their pages are shared, scripts/gqa_overlap.py),
-// so their workgroups should sit on the SAME XCD, at the same time: the host picks `xcd_period` such that grid rows
-// y, y + period, y + 2 period, ... (same XCD for every chunk index) serve a run of consecutive query heads.
-// (head_dim 256 keeps twice the K/V registers in flight per lane: its 8-wave instantiations are built for 2 waves per SIMD
-// -- up to 256 VGPRs, one workgroup per CU -- instead of spilling 41-46 registers to scratch at the 128 of 4 waves per SIMD)
-template <int D, int S_T, int FC, int NW, int VF = -1>
-__global__ __launch_bounds__(NW* kWave, (D >= 256 && NW >= 8) ? NW / 4 : NW / 2) void sparse_decode_kernel(QUEST_DECODE_HEAD_PARAMS, DecodeParams p) {
-    QUEST_DECODE_HEAD_TAKE(p);
-    uint32_t hq = blockIdx.y;
-    const uint32_t period = p.xcd_period & 255u, slow = (p.xcd_period >> 8) & 15u, group_l2 = p.xcd_period >> 12;
-    if (period > 1) {
-        hq = (hq % period) * (a_num_qo_heads / period) + hq / period;
-    } else if (slow) {
-        // slow-class kv heads first (plan_decode): the first quarter of the rows serves the kv heads = slow - 1 mod 4 (with
-        // all query heads of their groups), the rest follow in order
-        const uint32_t sr = slow - 1u, unit = hq >> group_l2, quarter = a_num_qo_heads >> (2u + group_l2);
-        uint32_t hk;
-        if (unit < quarter) {
-            hk = 4u * unit + sr;
-        } else {
-            const uint32_t r = unit - quarter;
-            hk = 4u * (r / 3u) + ((sr + 1u + r % 3u) & 3u);
-        }
-        hq = (hk << group_l2) + (hq & ((1u << group_l2) - 1u));
-    }
-    p.xcd_period = period;
-    if constexpr (VF == 8) sparse_decode_tiles_body<D, NW>(p, blockIdx.x, hq, blockIdx.z, a_num_qo_heads);
-    else sparse_decode_body<D, S_T, FC, NW, VF>(p, blockIdx.x, hq, blockIdx.z, a_num_qo_heads);
-}
-
-// One launch per layer of a batched step: the workgroup of a (sequence, query head) appends, scores its head's pages into
-// LDS, selects from LDS and gathers (layer_device.cuh).  grid (1, Hq, n_seqs) -- the per-head-list kernel's, so the same
-// XCD-aware row order applies.
-template <int D, int FC, int NW>
-__global__ __launch_bounds__(NW* kWave, NW / 2) void layer_decode_kernel(QUEST_LAYER_HEAD_PARAMS, LayerParams p) {
-    layer_decode_body<D, FC, NW>(a_q, a_state, a_meta, a_meta_tables, a_kv_tables, a_n_cap, a_meta_table_stride,
-                                 a_kv_table_stride, a_pack, a_num_qo_heads, p);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Group-shared variant: all GS query heads of a kv head attend the SAME page list (full-KV decode: the
-// model's dense first layers, contexts shorter than the budget).  One workgroup per (chunk, kv head)
-// fetches each K/V tile once and folds it into GS online-softmax states, instead of once per query head
-// as the per-head-list kernel above would (4x the traffic at Llama-3 GQA).  Same work split, same partial
-// records, same merge kernel.
-//
-// APPEND (round 4): the decode append rides in the same launch.  The reference issues append_kv_cache_decode and the
-// attention as two calls (QuestAttention.py:106 then :125-132, page.cu:6-99); here a dense layer of a captured step was
-// three launches (append, attention, merge).  The new token's row of the current page is touched by exactly ONE
-// workgroup per kv head -- the one whose chunk holds the last slot -- so that workgroup takes the row from the inputs
-// instead of from the pool, writes it to the pool and folds the key into the page's (max, min) metadata entry
-// (append_decode_body's arithmetic, same bits); nobody else reads or writes those bytes during the launch.
-template <int D, int GS, int NW, bool APPEND = false>
-__global__ __launch_bounds__(NW* kWave, NW / 2) void shared_decode_kernel(QUEST_DECODE_HEAD_PARAMS, DecodeParams p) {
-    // MHA (one query head per kv head: registers to spare): the next page's rows are requested before the current page is
-    // folded.  cfg 2: 14.35 -> 14.11 us per launch, 16.40 -> 16.20 per layer; the 32K dense launch 85.0 -> 84.4 us
-    // (profiles/r05_ab_dense_kernel_prefetch.txt).
-    constexpr bool PREFETCH = GS == 1;
-    QUEST_DECODE_HEAD_TAKE(p);
-    constexpr int LPR = D / kVec, R = kWave / LPR, S_T = 16, T = (S_T + R - 1) / R;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
-    const int row = lane / LPR, col = lane % LPR;
-    // grid order (launch_shared): (chunks, kv heads) or, with the NHD pool, (kv heads, chunks) -- p.xcd_period != 0, the
-    // preloaded field the per-head kernel uses for its own grid order -- so that workgroups adjacent in dispatch order read
-    // the 256-byte pieces of the SAME token rows next to each other (a page's rows are 8 KiB of heads side by side)
-    const bool heads_first = p.xcd_period != 0;
-    const uint32_t chunk = heads_first ? blockIdx.y : blockIdx.x, hk = heads_first ? blockIdx.x : blockIdx.y;
-    const SeqView sv = select_sequence(p, a_num_qo_heads, D, blockIdx.z);
-    if (p.state) {  // state-driven launch: the plan (chunks) was made for the pool capacity; workgroups whose
-                    // chunk lies past the live page list write an empty partial (weight 0 in the merge)
-        const quest_step_state_t st = *sv.state;
-        p.n_sel = (uint32_t)(st.n_pages - 1);
-        p.last_page_len = (uint32_t)st.kv_last_page_len;
-        p.last_page_idx = st.kv_last_page_idx;
-        if constexpr (APPEND) {
-            p.meta_last_page_len = (uint32_t)st.meta_last_page_len;
-            p.meta_last_page_idx = st.meta_last_page_idx;
-        }
-    }
-    const uint32_t n_slots = p.n_sel + 1;
-    const uint32_t slot_begin = min(n_slots, chunk * p.pages_per_chunk);
-    const uint32_t slot_end = min(n_slots, slot_begin + p.pages_per_chunk);
-
-    float8 qv[GS];
-#pragma unroll
-    for (int g = 0; g < GS; ++g) {
-        qv[g] = to_f32(ld8(sv.q + ((size_t)hk * GS + g) * D + col * kVec));
-        qv[g] *= p.scale_log2;
-    }
-    // page base + uni[t] + lane_off (+ v_off): the walk of quest_common.cuh (walk_*), the same for every pool layout
-    const uint32_t lane_off = walk_lane_off(p.st, hk, R, row, col * kVec);
-    const uint32_t v_off = pool_v_off(p.st, hk);
-    uint32_t uni[T];
-#pragma unroll
-    for (int t = 0; t < T; ++t) uni[t] = walk_uniform(p.st, hk, R, t);
-    RowState<D> st[GS];
-
-    [[maybe_unused]] const size_t app_in_off = ((size_t)blockIdx.z * (a_num_qo_heads / GS) + hk) * D + col * kVec;
-    // APPEND: the lanes (of the ONE wave per kv head that attends the current page) that hold the new token's row.  Their
-    // metadata loads are issued here and consumed after the page loop; the stores come after the loop as well -- issued in
-    // front of it they sat in the wave's vmcnt queue ahead of its K/V loads, whose first wait then also waited for the
-    // write acknowledgements (measured: the fused launch lost its gain whenever the last chunk was long).
-    [[maybe_unused]] bool app_mine = false;
-    [[maybe_unused]] uint16_t* app_mmax = nullptr;
-    [[maybe_unused]] ushort8 app_mx = (ushort8)(kHalfNegMax), app_mn = (ushort8)(kHalfMax);
-    if constexpr (APPEND) {
-        const uint32_t e = p.last_page_len - 1u;
-        app_mine = slot_begin <= p.n_sel && p.n_sel < slot_end && (uint32_t)wave == (p.n_sel - slot_begin) % NW &&
-                   (uint32_t)row == e % R;
-        if (app_mine) {
-            // metadata entry of the page: entry meta_last_page_len - 1 of the last metadata page (same pool geometry as
-            // the KV pool); a token that opens a page starts from the sentinels, not from stale pool bytes
-            const uint32_t me = p.meta_last_page_len - 1u;
-            app_mmax = reinterpret_cast<uint16_t*>(p.app_meta) + (size_t)p.meta_last_page_idx * p.st.page +
-                       (size_t)pool_slot(p.st, hk, me) * p.st.head + (size_t)me * p.st.entry + col * kVec;
-            if (e > 0) {
-                app_mx = *reinterpret_cast<const ushort8*>(app_mmax);
-                app_mn = *reinterpret_cast<const ushort8*>(app_mmax + v_off);
-            }
-        }
-    }
-
-    // request the K/V rows of slot s0
-    auto issue = [&](uint32_t s0, half8 (&k)[T], half8 (&v)[T]) {
-        const int32_t pg = __builtin_amdgcn_readfirstlane(s0 < p.n_sel ? sv.indices[s0] : p.last_page_idx);
-        const half_t* b0 = p.kv + (size_t)pg * p.st.page;
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            k[t] = ld8_stream(b0 + uni[t] + lane_off);
-            v[t] = ld8_stream(b0 + uni[t] + lane_off + v_off);
-        }
-    };
-    // fold the rows of slot s0 into the GS states
-    auto fold = [&](uint32_t s0, half8 (&k)[T], half8 (&v)[T]) {
-        const int len = s0 < p.n_sel ? S_T : (int)p.last_page_len;
-        if constexpr (APPEND) {
-            if (s0 >= p.n_sel) {  // wave-uniform: the current page -- its newest row is the token being decoded, which is
-                                  // not in the pool yet (written after this loop): it comes from the inputs
-                const uint32_t e = (uint32_t)len - 1u;
-                const half8 kn = ld8(p.app_k + app_in_off), vn = ld8(p.app_v + app_in_off);
-#pragma unroll
-                for (int t = 0; t < T; ++t)
-                    if ((uint32_t)(t * R + row) == e) {
-                        k[t] = kn;
-                        v[t] = vn;
-                    }
-            }
-        }
-        float8 kf[T], vf[T];
-        bool valid[T];
-#pragma unroll
-        for (int t = 0; t < T; ++t) {
-            valid[t] = row < len - t * R;
-            kf[t] = to_f32(k[t]);
-            vf[t] = valid[t] ? to_f32(v[t]) : (float8)(0.f);  // stale rows past the page length: select
-        }
-#pragma unroll
-        for (int g = 0; g < GS; ++g) {
-            float sc[T];
-            float m_new = st[g].m;
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                float dot = 0.f;
-#pragma unroll
-                for (int i = 0; i < kVec; ++i) dot = __builtin_fmaf(qv[g][i], kf[t][i], dot);
-                dot = row_allreduce_sum_fast<LPR>(dot);
-                sc[t] = valid[t] ? dot : kNegFloor;
-                m_new = __builtin_fmaxf(m_new, sc[t]);
-            }
-            const float scale = __builtin_amdgcn_exp2f(st[g].m - m_new);
-            st[g].d *= scale;
-            st[g].acc *= scale;
-#pragma unroll
-            for (int t = 0; t < T; ++t) {
-                const float pr = valid[t] ? __builtin_amdgcn_exp2f(sc[t] - m_new) : 0.f;
-                st[g].d += pr;
-#pragma unroll
-                for (int i = 0; i < kVec; ++i) st[g].acc[i] = __builtin_fmaf(pr, vf[t][i], st[g].acc[i]);
-            }
-            st[g].m = m_new;
-        }
-    };
-    if constexpr (PREFETCH) {
-        // the next page's rows are requested before the current page is folded (two register sets, 16 loads in flight per
-        // lane); same pages in the same order per wave, hence the same bits.  Straight-line issue -> fold segments: a load
-        // under a branch would be waited for at the join
-        uint32_t s0 = slot_begin + wave;
-        if (s0 < slot_end) {
-            half8 k0[T], v0[T], k1[T], v1[T];
-            issue(s0, k0, v0);
-            while (true) {
-                uint32_t s1 = s0 + NW;
-                if (s1 >= slot_end) {
-                    fold(s0, k0, v0);
-                    break;
-                }
-                issue(s1, k1, v1);
-                fold(s0, k0, v0);
-                s0 = s1 + NW;
-                if (s0 >= slot_end) {
-                    fold(s1, k1, v1);
-                    break;
-                }
-                issue(s0, k0, v0);
-                fold(s1, k1, v1);
-            }
-        }
-    } else {
-        for (uint32_t s0 = slot_begin + wave; s0 < slot_end; s0 += NW) {
-            half8 k[T], v[T];
-            issue(s0, k, v);
-            fold(s0, k, v);
-        }
-    }
-
-    if constexpr (APPEND) {
-        if (app_mine) {  // write the new token to the pool and fold its key into the page's (max, min) entry
-            const uint32_t e = p.last_page_len - 1u;
-            const half8 kn = ld8(p.app_k + app_in_off), vn = ld8(p.app_v + app_in_off);
-            half_t* dst = const_cast<half_t*>(p.kv) + (size_t)p.last_page_idx * p.st.page + lane_off + walk_uniform(p.st, hk, R, e / R);
-            st8(dst, kn);
-            st8(dst + v_off, vn);
-            const ushort8 k8 = __builtin_bit_cast(ushort8, kn);
-            *reinterpret_cast<ushort8*>(app_mmax) = fold_max(app_mx, k8);
-            *reinterpret_cast<ushort8*>(app_mmax + v_off) = fold_min(app_mn, k8);
-        }
-    }
-
-    __shared__ float s_acc[NW][GS][D];
-    __shared__ float s_md[NW][GS][2];
-#pragma unroll
-    for (int g = 0; g < GS; ++g) {
-        for_each_row_distance<LPR>([&](auto off_c) {  // rows of the wave -> one state
-            constexpr int OFF = decltype(off_c)::value;
-            const float m_o = lane_xor<OFF>(st[g].m, lane), d_o = lane_xor<OFF>(st[g].d, lane);
-            const float m_n = __builtin_fmaxf(st[g].m, m_o);
-            const float a = __builtin_amdgcn_exp2f(st[g].m - m_n), b = __builtin_amdgcn_exp2f(m_o - m_n);
-            st[g].d = st[g].d * a + d_o * b;
-#pragma unroll
-            for (int i = 0; i < kVec; ++i) st[g].acc[i] = st[g].acc[i] * a + lane_xor<OFF>(st[g].acc[i], lane) * b;
-            st[g].m = m_n;
-        });
-        if (row == 0) {
-#pragma unroll
-            for (int i = 0; i < kVec; ++i) s_acc[wave][g][col * kVec + i] = st[g].acc[i];
-            if (col == 0) {
-                s_md[wave][g][0] = st[g].m;
-                s_md[wave][g][1] = st[g].d;
-            }
-        }
-    }
-    __syncthreads();
-    for (uint32_t t = threadIdx.x; t < (uint32_t)(GS * D); t += NW * kWave) {
-        const uint32_t g = t / D, f = t % D, hq = hk * GS + g;
-        float M = s_md[0][g][0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) M = __builtin_fmaxf(M, s_md[w][g][0]);
-        float acc = 0.f, den = 0.f;
-#pragma unroll
-        for (int w = 0; w < NW; ++w) {
-            const float e = __builtin_amdgcn_exp2f(s_md[w][g][0] - M);
-            acc += e * s_acc[w][g][f];
-            den += e * s_md[w][g][1];
-        }
-        if (p.n_chunks == 1) {
-            sv.o[(size_t)hq * D + f] = (half_t)(acc / den);
-            if (p.lse && f == 0) sv.lse[hq] = (M + __builtin_amdgcn_logf(den)) * 0.6931471805599453f;
-        } else {
-            float* w = sv.ws + ((size_t)hq * p.n_chunks + chunk) * p.ws_stride;
-            w[f] = acc;
-            if (f == 0) {
-                w[D] = M;
-                w[D + 1] = den;
-            }
-        }
-    }
-}
-
-// Merge the per-chunk partial states of a head, normalise, cast to fp16 (the job of flashinfer's
-// VariableLengthMergeStates).  kMergeGroups thread groups each take every kMergeGroups-th chunk with all of
-// their loads independent (unrolled), then combine through LDS: two memory round trips total.
-// Merging INSIDE the attention launch (the workgroup of a head that draws the last arrival ticket merges; partial
-// records leave by write-through stores) was built twice -- round 1, and round 3 with the recipe of VERDICT r2 item 1a
-// -- bit-identical and slower: every workgroup's tail gains a store acknowledgement and an atomic round trip that
-// queue behind the launch's own streaming reads.  Same box, us per launch incl. merge: cfg 3 14.7 (this launch) vs
-// 22.4 (in-kernel), cfg 2 17.7 vs 20.6, cfg 4 23.8 vs 26.9 (gpurun_out/r3a_*).
-template <int D>
-__global__ __launch_bounds__(D* kMergeGroups) void merge_states_kernel(const float* __restrict__ ws,
-                                                                        half_t* __restrict__ o,
-                                                                        float* __restrict__ lse, uint32_t n_chunks,
-                                                                        uint32_t ws_stride, StepAdvance adv) {
-    __shared__ float s_w[1024];  // per-chunk weight exp2(m_c - M); planner keeps n_chunks <= 1024
-    __shared__ float s_red[kMergeGroups][D + 1];
-    __shared__ float s_M;
-    const uint32_t hq = blockIdx.x, tid = threadIdx.x;
-    const uint32_t f = tid % D, g = tid / D;
-    const float* w = ws + (size_t)hq * n_chunks * ws_stride;
-    // the next step's reservation (StepAdvance, append_device.cuh): nothing in or after this launch reads the state
-    if (adv.st && hq == 0 && tid < adv.batch.n_seqs)
-        step_state_advance_one(adv.st + tid, adv.kv_table + (size_t)tid * adv.batch.kv_table_stride,
-                               adv.meta_table + (size_t)tid * adv.batch.meta_table_stride, adv.page_size, adv.max_kv_pages,
-                               adv.max_meta_pages);
-    if (n_chunks <= kMergeFastChunks) {  // launch-uniform
-        merge_head_fast<D, D * kMergeGroups>(w, o + (size_t)hq * D, lse ? lse + hq : nullptr, n_chunks, ws_stride, tid,
-                                                    &s_red[0][0]);
-        return;
-    }
-    // the first kPre partial rows of this thread's chunks are requested up front
-    constexpr int kPre = kMergePre;
-    float pre[kPre];
-#pragma unroll
-    for (int j = 0; j < kPre; ++j) {
-        const uint32_t c = g + j * kMergeGroups, cc = c < n_chunks ? c : n_chunks - 1;  // clamped: no branch
-        pre[j] = w[(size_t)cc * ws_stride + f];
-    }
-    // pass 1: chunk maxima -> M, weights, denominator
-    float M = kNegFloor;
-    for (uint32_t c = tid; c < n_chunks; c += blockDim.x) M = __builtin_fmaxf(M, w[(size_t)c * ws_stride + D]);
-    M = wave_allreduce_max(M, (int)(tid & 63));
-    if ((tid & 63) == 0) s_red[0][tid >> 6] = M;
-    __syncthreads();
-    if (tid == 0) {
-        float mm = s_red[0][0];
-        for (uint32_t i = 1; i < (blockDim.x >> 6); ++i) mm = __builtin_fmaxf(mm, s_red[0][i]);
-        s_M = mm;
-    }
-    __syncthreads();
-    M = s_M;
-    float den = 0.f;
-    for (uint32_t c = tid; c < n_chunks; c += blockDim.x) {
-        const float e = __builtin_amdgcn_exp2f(w[(size_t)c * ws_stride + D] - M);
-        s_w[c] = e;
-        den += e * w[(size_t)c * ws_stride + D + 1];
-    }
-    __syncthreads();
-    // pass 2: weighted sum of the partial outputs
-    float acc = 0.f;
-#pragma unroll
-    for (int j = 0; j < kPre; ++j) {
-        const uint32_t c = g + j * kMergeGroups;
-        if (c < n_chunks) acc += s_w[c] * pre[j];
-    }
-#pragma unroll 8
-    for (uint32_t c = g + kPre * kMergeGroups; c < n_chunks; c += kMergeGroups)
-        acc += s_w[c] * w[(size_t)c * ws_stride + f];
-    den = wave_allreduce_sum(den, (int)(tid & 63));
-    s_red[g][f] = acc;
-    __shared__ float s_den[16];
-    if ((tid & 63) == 0) s_den[tid >> 6] = den;
-    __syncthreads();
-    if (g == 0) {
-        float a = s_red[0][f];
-#pragma unroll
-        for (int j = 1; j < kMergeGroups; ++j) a += s_red[j][f];
-        float dn = 0.f;
-        for (uint32_t i = 0; i < (blockDim.x >> 6); ++i) dn += s_den[i];
-        o[(size_t)hq * D + f] = (half_t)(a / dn);
-        if (lse && f == 0) lse[hq] = (M + __builtin_amdgcn_logf(dn)) * 0.6931471805599453f;
-    }
-}
-
-}  // namespace quest
+#include "decode_kernels.cuh"
+#include "pool_check.h"
 
 using namespace quest;
-
-namespace quest {
-int check_pool(const quest_paged_kv_t& p);  // append.hip
-}
 
 struct quest_decode_handler {
     uint32_t layout = 0;
@@ -450,6 +79,17 @@ static int flush_armed_advance(quest_decode_handler* h, hipStream_t s) {
 // launch).
 static uint32_t target_workgroups(const quest_decode_handler* h) { return h->batch > 1 ? h->num_cus : 2 * h->num_cus; }
 static constexpr uint32_t kMaxChunks = 1024;  // merge kernel's LDS weight table
+// Pages per workgroup when the `n_slots` pages of a head are cut for `workgroups` workgroups (at most `cap` pages each,
+// unless the split is forced: quest_decode_set_pages_per_chunk), in no more than kMaxChunks pieces.
+static uint32_t split_pages(uint32_t n_slots, uint32_t workgroups, uint32_t forced_ppc, uint32_t cap) {
+    uint32_t chunks = workgroups < 1 ? 1 : workgroups;
+    if (chunks > n_slots) chunks = n_slots;
+    if (chunks > kMaxChunks) chunks = kMaxChunks;
+    uint32_t ppc = forced_ppc ? forced_ppc : (n_slots + chunks - 1) / chunks;
+    if (!forced_ppc && ppc > cap) ppc = cap;
+    if ((n_slots + ppc - 1) / ppc > kMaxChunks) ppc = (n_slots + kMaxChunks - 1) / kMaxChunks;
+    return ppc;
+}
 extern "C" int quest_decode_arm_step_advance(quest_decode_handler_t* h, quest_step_state_t* state, const int32_t* kv_tables,
                                              const int32_t* meta_tables, uint32_t page_size, uint32_t max_kv_pages,
                                              uint32_t max_meta_pages, quest_batch_t batch) {
@@ -480,7 +120,7 @@ extern "C" int quest_decode_handler_create(quest_decode_handler_t** out, uint32_
         h->num_cus = (uint32_t)cus;
     else
         (void)hipGetLastError();  // no device (CPU-only import): keep the MI355X default
-    if (const char* e = quest_tuning_env("QUEST_DEC_WAVES")) h->dec_waves = atoi(e) == 8 ? 8 : 4;  // tuning knob
+    h->dec_waves = quest_tuning_int("QUEST_DEC_WAVES", 4) == 8 ? 8 : 4;  // tuning knob, read per handler
     *out = h;
     return 0;
 }
@@ -536,33 +176,15 @@ extern "C" int quest_decode_begin_forward(quest_decode_handler_t* h, uint32_t n_
     h->head_dim = head_dim;
     h->page_size = page_size;
     const uint32_t n_slots = n_selected_pages + 1;
-    uint32_t ppc;
-    if (h->forced_ppc) {
-        ppc = h->forced_ppc;
-    } else {
-        // a batch brings its own parallelism: the workgroups are spread over the sequences (fewer, longer
-        // chunks per head -> fewer partials and fewer repeats of the fused selection)
-        uint32_t chunks = target_workgroups(h) / (num_qo_heads * h->batch);
-        if (chunks < 1) chunks = 1;
-        if (chunks > n_slots) chunks = n_slots;
-        ppc = (n_slots + chunks - 1) / chunks;
-        // keep the fused front end usable for every plan (it stages one chunk's page ids in LDS): eager callers
-        // can fall back to two launches, the state-driven / batched entries cannot
-        if (ppc > (uint32_t)kFusedMaxPpc) ppc = kFusedMaxPpc;
-    }
-    if ((n_slots + ppc - 1) / ppc > kMaxChunks) ppc = (n_slots + kMaxChunks - 1) / kMaxChunks;
-    h->pages_per_chunk = ppc;
-    h->n_chunks = (n_slots + ppc - 1) / ppc;
-    {   // the group-shared kernel runs one workgroup per (chunk, KV head): plan it for the same 512 workgroups
-        uint32_t chunks = 2 * h->num_cus / (num_kv_heads * h->batch);
-        if (chunks < 1) chunks = 1;
-        if (chunks > n_slots) chunks = n_slots;
-        if (chunks > kMaxChunks) chunks = kMaxChunks;
-        uint32_t sp = h->forced_ppc ? h->forced_ppc : (n_slots + chunks - 1) / chunks;
-        if ((n_slots + sp - 1) / sp > kMaxChunks) sp = (n_slots + kMaxChunks - 1) / kMaxChunks;
-        h->shared_ppc = sp;
-        h->shared_chunks = (n_slots + sp - 1) / sp;
-    }
+    // a batch brings its own parallelism: the workgroups are spread over the sequences (fewer, longer chunks per head ->
+    // fewer partials and fewer repeats of the fused selection).  The cap keeps the fused front end usable for every plan
+    // (it stages one chunk's page ids in LDS): eager callers can fall back to two launches, the state-driven / batched
+    // entries cannot
+    h->pages_per_chunk = split_pages(n_slots, target_workgroups(h) / (num_qo_heads * h->batch), h->forced_ppc, kFusedMaxPpc);
+    h->n_chunks = (n_slots + h->pages_per_chunk - 1) / h->pages_per_chunk;
+    // the group-shared kernel runs one workgroup per (chunk, KV head): plan it for the same 512 workgroups
+    h->shared_ppc = split_pages(n_slots, 2 * h->num_cus / (num_kv_heads * h->batch), h->forced_ppc, n_slots);
+    h->shared_chunks = (n_slots + h->shared_ppc - 1) / h->shared_ppc;
     h->ws_stride = (head_dim + 2 + 31) / 32 * 32;
     const uint32_t max_chunks = h->n_chunks > h->shared_chunks ? h->n_chunks : h->shared_chunks;
     const size_t need = (size_t)h->batch * num_qo_heads * max_chunks * h->ws_stride * sizeof(float);
@@ -618,6 +240,231 @@ extern "C" int quest_decode_last_launch_info(const quest_decode_handler_t* h, ui
     return 0;
 }
 
+// One attention launch as the entries hand it to decode_entry / shared_entry / the one-launch layer: every operand by name.
+struct DecodeRequest {
+    const void* q = nullptr;
+    void* o = nullptr;
+    quest_paged_kv_t kv = {};
+    uint32_t num_qo_heads = 0;
+    float* lse = nullptr;
+    const void* scores = nullptr;  // fused top-k front end: the score rows (else the page ids come from kv.indices)
+    uint32_t n_scores = 0, score_stride = 0, tile_off = 0;
+    void* topk_val_out = nullptr;
+    int32_t* topk_idx_out = nullptr;
+    const quest_step_state_t* state = nullptr;
+    quest_batch_t batch = {1, 0, 0, 0};
+    const void *app_k = nullptr, *app_v = nullptr;  // optional decode append riding in the launch, with its metadata pool
+    quest_paged_kv_t metadata = {};
+};
+
+static DecodeRequest attention_request(const void* q, void* o, const quest_paged_kv_t& kv, uint32_t num_qo_heads, float* lse) {
+    DecodeRequest r;
+    r.q = q, r.o = o, r.kv = kv, r.num_qo_heads = num_qo_heads, r.lse = lse;
+    return r;
+}
+
+// ---- the request checks
+enum class Route { kHeadLists, kSharedList, kLayer };  // which page lists the launch reads: per query head / one / the tables
+
+// A request against the handler's plan, in the order the entries' return codes promise: no plan or a plan for fewer
+// sequences (ESTATE) before the operands, the operands before the geometry.  Puts the placeholders of a state-driven
+// launch into the pools.
+static int check_request(const quest_decode_handler* h, DecodeRequest& r, Route route) {
+    quest_paged_kv_t& kv = r.kv;
+    if (!h || r.batch.n_seqs == 0) return QUEST_EINVAL;
+    if (r.state) kv.last_page_len = 1;  // placeholder; the kernel reads the real one from `state`
+    if (!h->started) return QUEST_ESTATE;
+    if (r.batch.n_seqs > h->batch) return QUEST_ESTATE;  // workspace / plan were made for fewer sequences
+    if (!r.q || !r.o || !kv.data) return QUEST_EINVAL;
+    if (route == Route::kLayer) {
+        // the append and the estimate address the metadata pool with the KV pool's strides: same geometry required
+        if (int e = check_pool_pair(kv, r.metadata, true, true)) return e;
+    } else if (r.scores) {
+        if (!kv.indices || h->n_sel == 0 || h->n_sel > r.n_scores) return QUEST_EINVAL;
+        if (r.n_scores > QUEST_TOPK_MAX_ROW) return QUEST_ETOOLARGE;
+        if (h->pages_per_chunk > (uint32_t)kFusedMaxPpc) return QUEST_EUNSUPPORTED;
+        // (rows beyond 4096 columns need the second-generation front end, i.e. aligned score rows: choose_front_end)
+    } else if (h->n_sel > 0 && (!kv.indices || (route == Route::kHeadLists && !r.state && kv.page_budget < h->n_sel))) {
+        return QUEST_EINVAL;  // (state-driven: one shared list, row stride kv.page_budget == 0)
+    }
+    if (kv.layout != h->layout || kv.head_dim != h->head_dim || kv.page_size != h->page_size ||
+        kv.num_heads != h->num_kv_heads || r.num_qo_heads != h->num_qo_heads)
+        return QUEST_EINVAL;
+    if (kv.last_page_len == 0 || kv.last_page_len > kv.page_size) return QUEST_EINVAL;
+    return 0;
+}
+
+static float softmax_scale_log2(uint32_t head_dim) { return (float)(1.4426950408889634 / sqrt((double)head_dim)); }
+
+// What every attention launch passes to its kernel, whichever split of the plan (pages per chunk, chunks) it runs.
+static DecodeParams base_params(const quest_decode_handler* h, const DecodeRequest& r, uint32_t pages_per_chunk, uint32_t n_chunks) {
+    const quest_paged_kv_t& kv = r.kv;
+    DecodeParams p{};
+    p.q = (const half_t*)r.q, p.o = (half_t*)r.o, p.lse = r.lse;
+    p.kv = (const half_t*)kv.data, p.indices = kv.indices, p.st = pool_strides(kv);
+    p.last_page_len = kv.last_page_len, p.last_page_idx = kv.last_page_idx, p.page_size = kv.page_size;
+    p.group = r.num_qo_heads / kv.num_heads, p.scale_log2 = softmax_scale_log2(kv.head_dim);
+    p.n_sel = h->n_sel, p.pages_per_chunk = pages_per_chunk, p.n_chunks = n_chunks;
+    p.ws = h->ws, p.ws_stride = h->ws_stride, p.state = r.state, p.table_stride = r.batch.kv_table_stride;
+    return p;
+}
+
+// ---- the front-end choice
+// Everything the choice depends on, as values: no handler, no HIP.
+struct FrontEndInputs {
+    uintptr_t scores = 0, table = 0;   // addresses of the score rows (0: no fused front end) and of the page table(s)
+    uint32_t n_scores = 0, score_stride = 0, table_stride = 0, n_seqs = 1, page_size = 0, n_sel = 0, tile_off = 0;
+    uint32_t waves = 4;                // the handler's workgroup size (QUEST_DEC_WAVES)
+    int forced = 0;                    // quest_decode_set_front_end (0: by row length)
+};
+// fc: keys per thread of the fused front end's instantiation (0 = page ids come from an index tensor), waves = workgroup
+// size; the rest are the DecodeParams fields of the same names.
+struct FrontEnd {
+    int fc = 0;
+    uint32_t waves = 4, vec_front = 0, cpt = 0, stage_ids = 0, ids_lds_offset = 0, row_lead = 0, fe2_prefilter = 0, table_vec = 0;
+};
+
+static int choose_front_end(const FrontEndInputs& in, FrontEnd& fe) {
+    const uint32_t n_scores = in.n_scores, stride = in.score_stride;
+    const bool fused = in.scores != 0;
+    fe = FrontEnd{};
+    fe.waves = in.waves;
+    fe.stage_ids = n_scores <= 4096 ? 1u : 0u;  // keys always staged (2 B each); ids (4 B each) up to 16 KiB
+    fe.ids_lds_offset = (uint32_t)((((size_t)n_scores * 2) + 15) & ~(size_t)15);
+    int forced = 0;
+    bool aligned = false, table_aligned = false;  // score rows / page tables that vector loads can read
+    if (fused) {
+        // second-generation front end (topk_bitmap.cuh): 8-byte loads of 4 scores straight from the row -> the rows
+        // must be 8-byte aligned and readable up to the next multiple of 4 columns (the row stride covers it)
+        // Measured on MI355X (state-driven launches, us per launch gen 1 -> gen 2): cfg 3 (2047 columns, 16 workgroups
+        // per head) 12.7 -> 13.6, 8 x cfg 3 batched 47.9 -> 50.1, cfg 4 (8191 columns) 28.6 -> 21.9.  The second
+        // generation has fewer barriers but its per-wave scans are redundant work on an issue-bound CU (4 waves per
+        // SIMD), which costs more than it saves on short rows -> gen 2 from 4097 columns up (gen 1 spills there).
+        // quest_decode_set_front_end / QUEST_FRONT_END=1 / 2 force a generation where it is applicable (tuning, tests).
+        static const int env_forced = quest_tuning_int("QUEST_FRONT_END", 0);
+        forced = in.forced ? in.forced : env_forced;
+        aligned = (in.scores & 7u) == 0 && stride % 4u == 0 && stride >= ((n_scores + 3u) & ~3u);
+        table_aligned = (in.table & 15u) == 0 && (in.n_seqs == 1 || in.table_stride % 4u == 0);
+        fe.table_vec = table_aligned ? 1u : 0u;
+        int gen = 1;
+        bool lead_rows = false;
+        if (aligned) {
+            if (forced == 2 || forced == 3 || (forced == 0 && n_scores > 4096u)) gen = 2;
+        } else if (n_scores > 4096u && n_scores + 3u <= QUEST_TOPK_MAX_ROW && forced != 1) {  // (the bitmaps cover positions)
+            // the reference's own score layout beyond 4096 pages (contiguous [Hq][pages - 1] rows: 2-byte aligned,
+            // quest/utils/__init__.py:194): the second generation on the aligned stream BELOW each row (row_lead) -- one
+            // fused launch where rounds 2-4 needed topk_filtering + forward
+            gen = 2;
+            lead_rows = true;
+        }
+        if (gen != 1) {
+            fe.vec_front = 2;
+            fe.ids_lds_offset = 0;  // no key staging
+            fe.row_lead = lead_rows ? 1u : 0u;
+            // page ids are staged with 16-byte loads: the table(s) must be 16-byte aligned (and columns = positions)
+            if (!table_aligned || lead_rows) fe.stage_ids = 0;
+            // (gen 2 stages ids only in the instantiations with <= 16 keys per thread: rows <= 4096 columns)
+            // pre-filter of the histogram: pays where a thread holds many keys (rows beyond 4096 columns); QUEST_FE2_PREFILTER=0
+            // turns it off, =2 turns it on for every second-generation launch (tuning, tests)
+            static const int pre_env = quest_tuning_int("QUEST_FE2_PREFILTER", 1);
+            fe.fe2_prefilter = forced == 3 || pre_env == 2 || (pre_env == 1 && forced != 2 && n_scores > 4096u) ? 1u : 0u;
+        } else if (aligned && table_aligned && fe.stage_ids && forced != 1) {
+            fe.vec_front = 1;  // generation 1 with its staging arrays filled by the granule loads (8 / 16 bytes per lane)
+        }
+    }
+    // rows beyond 4096 columns are served by the second-generation front end only (the first one spills there):
+    // state-driven callers own the score scratch and give it an 8-byte aligned row stride (a multiple of 4 columns)
+    if (fused && !fe.vec_front && n_scores > 4096u && !in.tile_off) return QUEST_EUNSUPPORTED;
+    if (in.tile_off) {  // tiles front end (sparse_decode_tiles_body): the rows carry their tile maxima behind the scores
+        const uint32_t tiles_cap = (n_scores + 7u) / 8u;
+        if (!fused || in.tile_off != ((n_scores + 7u) & ~7u) || (in.scores & 15u) != 0 || stride % 8u != 0 ||
+            stride < in.tile_off + ((tiles_cap + 3u) & ~3u))
+            return QUEST_EINVAL;
+        if (in.page_size != 16 || in.n_sel > 256u || tiles_cap > 4u * 512u) return QUEST_EUNSUPPORTED;
+        fe.vec_front = 8;
+        fe.stage_ids = 0;
+        fe.ids_lds_offset = 0;
+    }
+    if (fused && fe.vec_front == 8u) {
+        fe.waves = 8;
+        fe.fc = 8;
+        fe.cpt = (n_scores + 7u) / 8u <= 2u * 512u ? 2u : 4u;  // tile keys per thread
+    } else if (fused) {
+        // the selection is VALU-issue bound (~1000 instructions per wave at 8 keys per thread), so rows
+        // beyond 1024 pages get 8 waves (<= 4 keys per thread up to 2048 pages, <= 8 up to 4096); the
+        // attention part runs the same with 4 or 8 waves.  Measured at cfg 3: 15.2 vs 15.8 us.
+        if (in.page_size == 16 && n_scores > 4u * 4u * kWave) fe.waves = 8;
+        const uint32_t nt = (in.page_size == 16 ? fe.waves : 4u) * kWave;
+        const uint32_t per_thread = (n_scores + (fe.row_lead ? 3u : 0u) + nt - 1) / nt;  // (+ the skipped leading columns)
+        // (24: rows of 8193-12288 columns at 512 threads -- cfg 4's capacity of ~8320 pages needs 17 keys per thread; the
+        // 32-key instantiation carries two more dead load / histogram / bitmap rounds in every unrolled phase.
+        // QUEST_FC24=0 takes the 32-key instantiation instead: A/B)
+        static const bool fc24 = quest_tuning_int("QUEST_FC24", 1) != 0;
+        fe.fc = per_thread <= 8 ? 8 : per_thread <= 16 ? 16 : (per_thread <= 24 && fc24) ? 24 : per_thread <= 32 ? 32 : 64;
+        // ownership chunk: a multiple of 4 columns when the register capacity allows, so a thread's keys are one
+        // 8/16-byte LDS read (topk_load_keys)
+        const uint32_t r4 = (per_thread + 3) / 4 * 4;
+        fe.cpt = r4 <= (uint32_t)fe.fc ? r4 : per_thread;
+        // rows of <= 8 columns per thread with vector-loadable chunks: each thread takes its own columns and page ids
+        // straight into registers (no staging arrays).  Measured (us per launch, staged -> direct): cfg 3 12.79 ->
+        // 12.38; 8 sequences batched 48.6 -> 48.85, cfg 5 51.2 -> 51.2 -> single-sequence launches only.
+        // QUEST_FE1_DIRECT=0 keeps the staged variant, =2 takes the direct one for batches too (tuning, tests).
+        static const int direct_env = quest_tuning_int("QUEST_FE1_DIRECT", 1);
+        const bool direct_ok = direct_env == 2 || (direct_env == 1 && in.n_seqs == 1);
+        const bool direct_possible = aligned && fe.vec_front != 2 && forced != 1 && fe.fc == 8 &&
+            (fe.cpt == 4 || (fe.cpt == 8 && (in.scores & 15u) == 0 && stride % 8u == 0 && stride >= ((n_scores + 7u) & ~7u)));
+        if (direct_possible && direct_ok && fe.vec_front == 1) fe.vec_front = 3;
+        // (Round 4 built two more front ends and measured both slower: column-range ownership -- a workgroup gathers the
+        // selected pages of ITS range of columns, no rank scan, no page-list hand-off: cfg 3 13.27 vs 12.07 us, cfg 4 20.34
+        // vs 19.54, the per-CU page imbalance costs more than the earlier page list returns -- and a third generation for
+        // long rows, pre-filter -> compact -> short-row select: 22.4 vs 19.6 us at cfg 4.  Removed from the tree in round 5,
+        // DESIGN.md 3.5; history: git log -S sparse_decode_colrange_body, -S fe3_select.)
+    }
+    return 0;
+}
+
+// ---- the grid row order
+// DecodeParams::xcd_period of a launch with `chunks_per_head` workgroups per query head.  slow_first_pool: the KV pool of
+// a single-sequence sparse_decode_kernel launch, the one kernel that honours the slow-class-first packing (else NULL).
+static uint32_t grid_row_order(uint32_t chunks_per_head, uint32_t num_qo_heads, uint32_t group, const quest_paged_kv_t* slow_first_pool) {
+    // XCD-aware row order for GQA (see sparse_decode_kernel); QUEST_XCD_GROUP=0 keeps the plain order (tuning)
+    static const bool xcd_group = quest_tuning_int("QUEST_XCD_GROUP", 1) != 0;
+    uint32_t gcd = 8, c = chunks_per_head % 8u;
+    while (c) { const uint32_t t = gcd % c; gcd = c; c = t; }
+    const uint32_t period = 8u / gcd;
+    uint32_t order = (xcd_group && group > 1 && period > 1 && num_qo_heads % period == 0 &&
+                      (num_qo_heads / period) % group == 0) ? period : 1u;
+    // Dispatch order by address class (round 5, scripts/probe/addr_class_probe.hip): on the NHD pool a head's K/V rows
+    // are 256-byte pieces at one offset inside every 1 KiB, and pieces whose address bits 8-9 are 01 are served ~20 %
+    // slower than the others under mixed traffic -- heads 1, 5, 9, ... of a 128-wide MHA pool.  A single sequence's
+    // launch is two workgroups per CU, dispatched rows-first: the first 16 rows' workgroups get ahead of the second
+    // 16 (they start their gather ~1 us earlier and finish ~2 us earlier), so the slow heads go FIRST, where they
+    // have that slack, instead of deciding the end of the launch from the second half.
+    // Measured at cfg 3, same box, us per launch: 12.04 -> 11.82 (profiles/r05_ab_slow_class_heads_first.txt);
+    // QUEST_SLOW_FIRST=0 keeps the plain order (A/B).  Same work per head, same bits.
+    static const int slow_env = quest_tuning_int("QUEST_SLOW_FIRST", 1);
+    if (const quest_paged_kv_t* kv = slow_first_pool)
+        if (slow_env && order == 1 && (group & (group - 1u)) == 0 && kv->layout == QUEST_LAYOUT_NHD && kv->head_dim == 128 &&
+            kv->num_heads % 4u == 0) {
+            const uint32_t c0 = (uint32_t)(((uintptr_t)kv->data >> 8) & 3u);  // class of kv head 0
+            order |= (1u + ((1u - c0) & 3u)) << 8 | (uint32_t)__builtin_ctz(group) << 12;
+        }
+    return order;
+}
+
+// ---- the launchers
+// Behind every attention launch: the merge of a head's partials (it carries the armed step advance) or, for a plan
+// without a merge launch, the advance as a launch of its own.
+template <int D>
+static int merge_and_advance(quest_decode_handler* h, const DecodeParams& p, uint32_t heads_x_seqs, float* lse, hipStream_t s) {
+    if (p.n_chunks > 1 && !h->skip_merge) {  // o / lse / partials of a batch are contiguous over (sequence, head): one grid
+        hipLaunchKernelGGL((merge_states_kernel<D>), dim3(heads_x_seqs), dim3(D * kMergeGroups), 0, s, (const float*)p.ws, p.o,
+                           lse, p.n_chunks, p.ws_stride, take_armed_advance(h));
+        QUEST_LAUNCH_CHECK();
+    }
+    return flush_armed_advance(h, s);
+}
+
 template <int D, int FC>
 static int launch_decode_fc(quest_decode_handler* h, const DecodeParams& p, uint32_t num_qo_heads, uint32_t waves,
                             hipStream_t s, uint32_t n_seqs) {
@@ -635,13 +482,14 @@ static int launch_decode_fc(quest_decode_handler* h, const DecodeParams& p, uint
     //   FC 8,  variant 8: tiles front end, rows that carry their tile maxima (cfg 4)
     //   FC 16 / 24 / 32, variant 2: second-generation front end of long rows without tile maxima
     // QUEST_FE_SPECIALIZE=0 launches the generic kernel instead (A/B).
-    static const bool specialize = [] { const char* e = quest_tuning_env("QUEST_FE_SPECIALIZE"); return !e || atoi(e) != 0; }();
-    if (p.vec_front == 8u) {  // tiles front end (plan_decode: page size 16, 8 waves)
+    static const bool specialize = quest_tuning_int("QUEST_FE_SPECIALIZE", 1) != 0;
+    float* const lse = QUEST_LSE_ENABLED ? p.lse : nullptr;
+    if (p.vec_front == 8u) {  // tiles front end (choose_front_end: page size 16, 8 waves)
         if constexpr (FC == 8) {
             info[3] = 1u;
             hipLaunchKernelGGL((sparse_decode_kernel<D, 16, 8, 8, 8>), grid, dim3(8 * kWave), 0, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
             QUEST_LAUNCH_CHECK();
-            goto merge;
+            return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s);
         } else {
             return QUEST_EUNSUPPORTED;
         }
@@ -653,12 +501,12 @@ static int launch_decode_fc(quest_decode_handler* h, const DecodeParams& p, uint
             if (p.vec_front == (uint32_t)VFA) {
                 hipLaunchKernelGGL((sparse_decode_kernel<D, 16, FC, 8, VFA>), grid, dim3(8 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
                 QUEST_LAUNCH_CHECK();
-                goto merge;
+                return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s);
             }
             if (VFB != VFA && p.vec_front == (uint32_t)VFB) {
                 hipLaunchKernelGGL((sparse_decode_kernel<D, 16, FC, 8, VFB>), grid, dim3(8 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
                 QUEST_LAUNCH_CHECK();
-                goto merge;
+                return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s);
             }
             info[3] = 0u;
         }
@@ -670,14 +518,7 @@ static int launch_decode_fc(quest_decode_handler* h, const DecodeParams& p, uint
     else
         hipLaunchKernelGGL((sparse_decode_kernel<D, 0, FC, 4>), grid, dim3(4 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
     QUEST_LAUNCH_CHECK();
-merge:
-    if (h->n_chunks > 1 && !h->skip_merge) {  // o / lse / partials of a batch are contiguous over (sequence, head): one grid
-        hipLaunchKernelGGL((merge_states_kernel<D>), dim3(num_qo_heads * n_seqs), dim3(D * kMergeGroups), 0, s,
-                           (const float*)p.ws, p.o, QUEST_LSE_ENABLED ? p.lse : nullptr, h->n_chunks, p.ws_stride,
-                           take_armed_advance(h));
-        QUEST_LAUNCH_CHECK();
-    }
-    return flush_armed_advance(h, s);
+    return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s);
 }
 
 // fc: fused top-k front end variant (0 = page ids come from an index tensor)
@@ -695,219 +536,50 @@ static int launch_decode(quest_decode_handler* h, const DecodeParams& p, uint32_
     }
 }
 
-// Checks + kernel parameters of a per-head-list decode launch; fc = keys per thread of the fused front end (0 = page ids
-// come from an index tensor), waves = workgroup size.
-static int plan_decode(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv, uint32_t num_qo_heads,
-                       const void* scores, uint32_t n_scores, void* topk_val_out, int32_t* topk_idx_out, float* lse,
-                       uint32_t score_stride, const quest_step_state_t* state, quest_batch_t batch, DecodeParams& p, int& fc,
-                       uint32_t& waves, uint32_t tile_off = 0) {
-    if (state) kv.last_page_len = 1;  // placeholder; the kernel reads the real one from `state`
-    if (!h || batch.n_seqs == 0) return QUEST_EINVAL;
-    if (!h->started) return QUEST_ESTATE;
-    if (batch.n_seqs > h->batch) return QUEST_ESTATE;  // workspace / plan were made for fewer sequences
-    if (!q || !o || !kv.data) return QUEST_EINVAL;
-    const bool fused = scores != nullptr;
-    if (fused) {
-        if (!kv.indices || h->n_sel == 0 || h->n_sel > n_scores) return QUEST_EINVAL;
-        if (n_scores > QUEST_TOPK_MAX_ROW) return QUEST_ETOOLARGE;
-        if (h->pages_per_chunk > (uint32_t)kFusedMaxPpc) return QUEST_EUNSUPPORTED;
-        // (rows beyond 4096 columns need the second-generation front end, i.e. aligned score rows: checked below)
-    } else if (h->n_sel > 0 && (!kv.indices || (!state && kv.page_budget < h->n_sel))) {
-        return QUEST_EINVAL;  // (state-driven: one shared list, row stride kv.page_budget == 0)
-    }
-    if (kv.layout != h->layout || kv.head_dim != h->head_dim || kv.page_size != h->page_size ||
-        kv.num_heads != h->num_kv_heads || num_qo_heads != h->num_qo_heads)
-        return QUEST_EINVAL;
-    if (kv.last_page_len == 0 || kv.last_page_len > kv.page_size) return QUEST_EINVAL;
-    p = DecodeParams{};
-    p.q = (const half_t*)q;
-    p.o = (half_t*)o;
-    p.lse = lse;
-    p.kv = (const half_t*)kv.data;
-    p.indices = kv.indices;
-    p.ws = h->ws;
-    p.st = pool_strides(kv);
+// A per-head-list decode launch: checks, kernel parameters, front end, row order, launch.
+static int decode_entry(quest_decode_handler* h, DecodeRequest r, hipStream_t s) {
+    if (int e = check_request(h, r, Route::kHeadLists)) return e;
+    const quest_paged_kv_t& kv = r.kv;
+    const bool fused = r.scores != nullptr;
+    DecodeParams p = base_params(h, r, h->pages_per_chunk, h->n_chunks);
     p.idx_stride = fused ? 0 : kv.page_budget;
-    p.n_sel = h->n_sel;
-    p.last_page_len = kv.last_page_len;
-    p.last_page_idx = kv.last_page_idx;
-    p.page_size = kv.page_size;
-    p.group = num_qo_heads / kv.num_heads;
-    p.pages_per_chunk = h->pages_per_chunk;
-    p.n_chunks = h->n_chunks;
-    p.scale_log2 = (float)(1.4426950408889634 / sqrt((double)kv.head_dim));
-    p.scores = (const uint16_t*)scores;
-    p.n_scores = n_scores;
-    p.sel_val_out = (uint16_t*)topk_val_out;
-    p.sel_idx_out = topk_idx_out;
-    if (fused && state && !topk_idx_out) {  // state-driven launches have no output arguments: handler-level aid
+    p.scores = (const uint16_t*)r.scores;
+    p.n_scores = r.n_scores;
+    p.sel_val_out = (uint16_t*)r.topk_val_out;
+    p.sel_idx_out = r.topk_idx_out;
+    if (fused && r.state && !r.topk_idx_out) {  // state-driven launches have no output arguments: handler-level aid
         p.sel_val_out = (uint16_t*)h->sel_val_out;
         p.sel_idx_out = h->sel_idx_out;
     }
     p.sel_stride = h->n_sel;
-    p.ws_stride = h->ws_stride;
-    p.score_stride = score_stride ? score_stride : n_scores;
-    p.stage_ids = n_scores <= 4096 ? 1u : 0u;  // keys always staged (2 B each); ids (4 B each) up to 16 KiB
-    p.ids_lds_offset = (uint32_t)((((size_t)n_scores * 2) + 15) & ~(size_t)15);
-    p.vec_front = 0;
-    int forced = 0;
-    bool table_vec = false, rows_aligned = false;
-    if (fused) {
-        // second-generation front end (topk_bitmap.cuh): 8-byte loads of 4 scores straight from the row -> the rows
-        // must be 8-byte aligned and readable up to the next multiple of 4 columns (the row stride covers it)
-        // Measured on MI355X (state-driven launches, us per launch gen 1 -> gen 2): cfg 3 (2047 columns, 16 workgroups
-        // per head) 12.7 -> 13.6, 8 x cfg 3 batched 47.9 -> 50.1, cfg 4 (8191 columns) 28.6 -> 21.9.  The second
-        // generation has fewer barriers but its per-wave scans are redundant work on an issue-bound CU (4 waves per
-        // SIMD), which costs more than it saves on short rows -> gen 2 from 4097 columns up (gen 1 spills there).
-        // quest_decode_set_front_end / QUEST_FRONT_END=1 / 2 force a generation where it is applicable (tuning, tests).
-        static const int env_forced = [] { const char* e = quest_tuning_env("QUEST_FRONT_END"); return e ? atoi(e) : 0; }();
-        forced = h->front_end ? h->front_end : env_forced;
-        const uint32_t stride = p.score_stride;
-        const bool aligned = ((uintptr_t)scores & 7u) == 0 && stride % 4u == 0 && stride >= ((n_scores + 3u) & ~3u);
-        const bool table_aligned = ((uintptr_t)kv.indices & 15u) == 0 && (batch.n_seqs == 1 || batch.kv_table_stride % 4u == 0);
-        table_vec = table_aligned;
-        rows_aligned = aligned;
-        int gen = 1;
-        bool lead_rows = false;
-        if (aligned) {
-            if (forced == 2 || forced == 3 || (forced == 0 && n_scores > 4096u)) gen = 2;
-        } else if (n_scores > 4096u && n_scores + 3u <= QUEST_TOPK_MAX_ROW && forced != 1) {  // (the bitmaps cover positions)
-            // the reference's own score layout beyond 4096 pages (contiguous [Hq][pages - 1] rows: 2-byte aligned,
-            // quest/utils/__init__.py:194): the second generation on the aligned stream BELOW each row (row_lead) -- one
-            // fused launch where rounds 2-4 needed topk_filtering + forward
-            gen = 2;
-            lead_rows = true;
-        }
-        if (gen != 1) {
-            p.vec_front = 2;
-            p.ids_lds_offset = 0;  // no key staging
-            p.row_lead = lead_rows ? 1u : 0u;
-            // page ids are staged with 16-byte loads: the table(s) must be 16-byte aligned (and columns = positions)
-            if (!table_aligned || lead_rows) p.stage_ids = 0;
-            // (gen 2 stages ids only in the instantiations with <= 16 keys per thread: rows <= 4096 columns)
-            // pre-filter of the histogram: pays where a thread holds many keys (rows beyond 4096 columns); QUEST_FE2_PREFILTER=0
-            // turns it off, =2 turns it on for every second-generation launch (tuning, tests)
-            static const int pre_env = [] { const char* e = quest_tuning_env("QUEST_FE2_PREFILTER"); return e ? atoi(e) : 1; }();
-            p.fe2_prefilter = forced == 3 || pre_env == 2 || (pre_env == 1 && forced != 2 && n_scores > 4096u) ? 1u : 0u;
-        } else if (aligned && table_aligned && p.stage_ids && forced != 1) {
-            p.vec_front = 1;  // generation 1 with its staging arrays filled by the granule loads (8 / 16 bytes per lane)
-        }
-    }
-    // rows beyond 4096 columns are served by the second-generation front end only (the first one spills there):
-    // state-driven callers own the score scratch and give it an 8-byte aligned row stride (a multiple of 4 columns)
-    if (fused && !p.vec_front && n_scores > 4096u && !tile_off) return QUEST_EUNSUPPORTED;
-    if (tile_off) {  // tiles front end (sparse_decode_tiles_body): the rows carry their tile maxima behind the scores
-        const uint32_t tiles_cap = (n_scores + 7u) / 8u;
-        if (!fused || tile_off != ((n_scores + 7u) & ~7u) || ((uintptr_t)scores & 15u) != 0 || p.score_stride % 8u != 0 ||
-            p.score_stride < tile_off + ((tiles_cap + 3u) & ~3u))
-            return QUEST_EINVAL;
-        if (kv.page_size != 16 || h->n_sel > 256u || tiles_cap > 4u * 512u) return QUEST_EUNSUPPORTED;
-        p.vec_front = 8;
-        p.stage_ids = 0;
-        p.ids_lds_offset = 0;
-    }
-    p.state = state;
-    p.table_stride = batch.kv_table_stride;
-    p.budgets = state ? batch.page_budgets : nullptr;
-    {   // XCD-aware row order for GQA (see sparse_decode_kernel); QUEST_XCD_GROUP=0 keeps the plain order (tuning)
-        static const bool xcd_group = [] { const char* e = quest_tuning_env("QUEST_XCD_GROUP"); return !e || atoi(e) != 0; }();
-        uint32_t gcd = 8, c = h->n_chunks % 8u;
-        while (c) { const uint32_t t = gcd % c; gcd = c; c = t; }
-        const uint32_t period = 8u / gcd;
-        p.xcd_period = (xcd_group && p.group > 1 && period > 1 && num_qo_heads % period == 0 &&
-                        (num_qo_heads / period) % p.group == 0) ? period : 1u;
-        // Dispatch order by address class (round 5, scripts/probe/addr_class_probe.hip): on the NHD pool a head's K/V rows
-        // are 256-byte pieces at one offset inside every 1 KiB, and pieces whose address bits 8-9 are 01 are served ~20 %
-        // slower than the others under mixed traffic -- heads 1, 5, 9, ... of a 128-wide MHA pool.  A single sequence's
-        // launch is two workgroups per CU, dispatched rows-first: the first 16 rows' workgroups get ahead of the second
-        // 16 (they start their gather ~1 us earlier and finish ~2 us earlier), so the slow heads go FIRST, where they
-        // have that slack, instead of deciding the end of the launch from the second half.
-        // Measured at cfg 3, same box, us per launch: 12.04 -> 11.82 (profiles/r05_ab_slow_class_heads_first.txt);
-        // QUEST_SLOW_FIRST=0 keeps the plain order (A/B).  Same work per head, same bits.
-        static const int slow_env = [] { const char* e = quest_tuning_env("QUEST_SLOW_FIRST"); return e ? atoi(e) : 1; }();
-        if (slow_env && p.xcd_period == 1 && (p.group & (p.group - 1u)) == 0 && kv.layout == QUEST_LAYOUT_NHD &&
-            kv.head_dim == 128 && kv.num_heads % 4u == 0 && batch.n_seqs == 1) {
-            const uint32_t c0 = (uint32_t)(((uintptr_t)kv.data >> 8) & 3u);  // class of kv head 0
-            p.xcd_period |= (1u + ((1u - c0) & 3u)) << 8 | (uint32_t)__builtin_ctz(p.group) << 12;
-        }
-    }
-    // fc > 0: capacity (keys per thread) of the fused top-k front end; 0 = page ids come from an index tensor
-    fc = 0;
-    waves = h->dec_waves;
-    p.cpt = 0;
-    if (fused && p.vec_front == 8u) {
-        waves = 8;
-        fc = 8;
-        p.cpt = (n_scores + 7u) / 8u <= 2u * 512u ? 2u : 4u;  // tile keys per thread
-        p.table_vec = table_vec ? 1u : 0u;
-    } else if (fused) {
-        // the selection is VALU-issue bound (~1000 instructions per wave at 8 keys per thread), so rows
-        // beyond 1024 pages get 8 waves (<= 4 keys per thread up to 2048 pages, <= 8 up to 4096); the
-        // attention part runs the same with 4 or 8 waves.  Measured at cfg 3: 15.2 vs 15.8 us.
-        if (kv.page_size == 16 && n_scores > 4u * 4u * kWave) waves = 8;
-        const uint32_t nt = (kv.page_size == 16 ? waves : 4u) * kWave;
-        const uint32_t per_thread = (n_scores + (p.row_lead ? 3u : 0u) + nt - 1) / nt;  // (+ the skipped leading columns)
-        // (24: rows of 8193-12288 columns at 512 threads -- cfg 4's capacity of ~8320 pages needs 17 keys per thread; the
-        // 32-key instantiation carries two more dead load / histogram / bitmap rounds in every unrolled phase.
-        // QUEST_FC24=0 takes the 32-key instantiation instead: A/B)
-        static const bool fc24 = [] { const char* e = quest_tuning_env("QUEST_FC24"); return !e || atoi(e) != 0; }();
-        fc = per_thread <= 8 ? 8 : per_thread <= 16 ? 16 : (per_thread <= 24 && fc24) ? 24 : per_thread <= 32 ? 32 : 64;
-        // ownership chunk: a multiple of 4 columns when the register capacity allows, so a thread's keys are one
-        // 8/16-byte LDS read (topk_load_keys)
-        const uint32_t r4 = (per_thread + 3) / 4 * 4;
-        p.cpt = r4 <= (uint32_t)fc ? r4 : per_thread;
-        // rows of <= 8 columns per thread with vector-loadable chunks: each thread takes its own columns and page ids
-        // straight into registers (no staging arrays).  Measured (us per launch, staged -> direct): cfg 3 12.79 ->
-        // 12.38; 8 sequences batched 48.6 -> 48.85, cfg 5 51.2 -> 51.2 -> single-sequence launches only.
-        // QUEST_FE1_DIRECT=0 keeps the staged variant, =2 takes the direct one for batches too (tuning, tests).
-        static const int direct_env = [] { const char* e = quest_tuning_env("QUEST_FE1_DIRECT"); return e ? atoi(e) : 1; }();
-        const bool direct_ok = direct_env == 2 || (direct_env == 1 && batch.n_seqs == 1);
-        const bool direct_possible = rows_aligned && p.vec_front != 2 && forced != 1 && fc == 8 &&
-            (p.cpt == 4 || (p.cpt == 8 && ((uintptr_t)scores & 15u) == 0 && p.score_stride % 8u == 0 &&
-                            p.score_stride >= ((n_scores + 7u) & ~7u)));
-        if (direct_possible && direct_ok && p.vec_front == 1) p.vec_front = 3;
-        // (Round 4 built two more front ends and measured both slower: column-range ownership -- a workgroup gathers the
-        // selected pages of ITS range of columns, no rank scan, no page-list hand-off: cfg 3 13.27 vs 12.07 us, cfg 4 20.34
-        // vs 19.54, the per-CU page imbalance costs more than the earlier page list returns -- and a third generation for
-        // long rows, pre-filter -> compact -> short-row select: 22.4 vs 19.6 us at cfg 4.  Removed from the tree in round 5,
-        // DESIGN.md 3.5; history: git log -S sparse_decode_colrange_body, -S fe3_select.)
-        p.table_vec = table_vec ? 1u : 0u;
-    }
-    return 0;
-}
-
-static int decode_entry(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
-                        uint32_t num_qo_heads, const void* scores, uint32_t n_scores, void* topk_val_out,
-                        int32_t* topk_idx_out, float* lse, hipStream_t s, uint32_t score_stride = 0,
-                        const quest_step_state_t* state = nullptr, quest_batch_t batch = {1, 0, 0, 0}, uint32_t tile_off = 0) {
-    DecodeParams p;
-    int fc;
-    uint32_t waves;
-    if (int e = plan_decode(h, q, o, kv, num_qo_heads, scores, n_scores, topk_val_out, topk_idx_out, lse, score_stride, state,
-                            batch, p, fc, waves, tile_off))
-        return e;
+    p.score_stride = r.score_stride ? r.score_stride : r.n_scores;
+    FrontEndInputs in;
+    in.scores = (uintptr_t)r.scores, in.table = (uintptr_t)kv.indices;
+    in.n_scores = r.n_scores, in.score_stride = p.score_stride, in.table_stride = r.batch.kv_table_stride;
+    in.n_seqs = r.batch.n_seqs, in.page_size = kv.page_size, in.n_sel = h->n_sel, in.tile_off = r.tile_off;
+    in.waves = h->dec_waves, in.forced = h->front_end;
+    FrontEnd fe;
+    if (int e = choose_front_end(in, fe)) return e;
+    p.vec_front = fe.vec_front, p.cpt = fe.cpt, p.stage_ids = fe.stage_ids, p.ids_lds_offset = fe.ids_lds_offset;
+    p.row_lead = fe.row_lead, p.fe2_prefilter = fe.fe2_prefilter, p.table_vec = fe.table_vec;
+    p.budgets = r.state ? r.batch.page_budgets : nullptr;
+    p.xcd_period = grid_row_order(h->n_chunks, r.num_qo_heads, p.group, r.batch.n_seqs == 1 ? &kv : nullptr);
     switch (kv.head_dim) {
-        case 64: return launch_decode<64>(h, p, num_qo_heads, fc, waves, s, batch.n_seqs);
-        case 128: return launch_decode<128>(h, p, num_qo_heads, fc, waves, s, batch.n_seqs);
-        case 256: return launch_decode<256>(h, p, num_qo_heads, fc, waves, s, batch.n_seqs);
+        case 64: return launch_decode<64>(h, p, r.num_qo_heads, fe.fc, fe.waves, s, r.batch.n_seqs);
+        case 128: return launch_decode<128>(h, p, r.num_qo_heads, fe.fc, fe.waves, s, r.batch.n_seqs);
+        case 256: return launch_decode<256>(h, p, r.num_qo_heads, fe.fc, fe.waves, s, r.batch.n_seqs);
         default: return QUEST_EUNSUPPORTED;
     }
 }
 
-extern "C" int quest_decode_forward(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
-                                    uint32_t num_qo_heads, float* lse, quest_stream_t stream) {
-    return decode_entry(h, q, o, kv, num_qo_heads, nullptr, 0, nullptr, nullptr, lse, (hipStream_t)stream);
-}
-
 template <int D>
-static int launch_shared(const quest_decode_handler* h, const DecodeParams& p_in, uint32_t num_qo_heads, uint32_t gs,
-                         hipStream_t s, uint32_t n_seqs) {
+static int launch_shared(quest_decode_handler* h, DecodeParams p, uint32_t num_qo_heads, uint32_t gs, hipStream_t s,
+                         uint32_t n_seqs) {
     // (8-wave workgroups for group sizes 1 / 2 -- 16 waves per CU instead of 8, each with one page in flight -- measured
     // slower in round 4: cfg 2 18.4 vs 17.8 us per layer, the 32K dense kernel 94.4 vs 92.4 us)
-    static const char* order_env = quest_tuning_env("QUEST_SHARED_HEADS_FIRST");
-    const bool nhd = p_in.st.head < p_in.st.entry;
+    static const char* order_env = quest_tuning_env("QUEST_SHARED_HEADS_FIRST");  // unset: by layout
+    const bool nhd = p.st.head < p.st.entry;
     const bool heads_first = order_env ? atoi(order_env) != 0 : nhd && num_qo_heads / gs > 1;
-    DecodeParams p = p_in;
     p.xcd_period = heads_first ? 1u : 0u;
     dim3 grid(p.n_chunks, num_qo_heads / gs, n_seqs), block(4 * kWave);
     if (heads_first) grid = dim3(num_qo_heads / gs, p.n_chunks, n_seqs);
@@ -927,100 +599,62 @@ static int launch_shared(const quest_decode_handler* h, const DecodeParams& p_in
     }
 #undef QUEST_SHARED_CASE
     QUEST_LAUNCH_CHECK();
-    if (p.n_chunks > 1 && !h->skip_merge) {
-        hipLaunchKernelGGL((merge_states_kernel<D>), dim3(num_qo_heads * n_seqs), dim3(D * kMergeGroups), 0, s,
-                           (const float*)p.ws, p.o, p.lse, p.n_chunks, p.ws_stride,
-                           take_armed_advance(const_cast<quest_decode_handler*>(h)));
-        QUEST_LAUNCH_CHECK();
-    }
-    return flush_armed_advance(const_cast<quest_decode_handler*>(h), s);
+    return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, p.lse, s);
 }
 
-struct SharedAppend {  // optional decode append riding in the group-shared launch
-    const void* k = nullptr;
-    const void* v = nullptr;
-    const quest_paged_kv_t* metadata = nullptr;
-};
-
-static int shared_entry(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv, uint32_t num_qo_heads,
-                        float* lse, const quest_step_state_t* state, quest_stream_t stream,
-                        quest_batch_t batch = {1, 0, 0, 0}, SharedAppend app = {}) {
-    if (!h || batch.n_seqs == 0) return QUEST_EINVAL;
-    if (state) kv.last_page_len = 1;  // placeholder; read from `state` in the kernel
-    if (!h->started) return QUEST_ESTATE;
-    if (batch.n_seqs > h->batch) return QUEST_ESTATE;
-    if (!q || !o || !kv.data || (h->n_sel > 0 && !kv.indices)) return QUEST_EINVAL;
-    if (kv.layout != h->layout || kv.head_dim != h->head_dim || kv.page_size != h->page_size ||
-        kv.num_heads != h->num_kv_heads || num_qo_heads != h->num_qo_heads)
-        return QUEST_EINVAL;
-    if (kv.last_page_len == 0 || kv.last_page_len > kv.page_size) return QUEST_EINVAL;
+static int shared_entry(quest_decode_handler* h, DecodeRequest r, hipStream_t s) {
+    if (int e = check_request(h, r, Route::kSharedList)) return e;
+    const quest_paged_kv_t& kv = r.kv;
     if (kv.page_size != 16 || (kv.head_dim != 64 && kv.head_dim != 128)) {
         // outside the group-shared kernel's set.  Eager callers get EUNSUPPORTED and pass the per-head index
         // tensor to quest_decode_forward; a state-driven launch has no such tensor, so it runs the per-head-list
         // kernel with every head reading the ONE page table (row stride 0) and the live length from `state`.
-        if (!state || app.k) return QUEST_EUNSUPPORTED;  // (with an append: the caller issues it as its own launch)
-        kv.page_budget = 0;
-        return decode_entry(h, q, o, kv, num_qo_heads, nullptr, 0, nullptr, nullptr, lse, (hipStream_t)stream, 0,
-                            state, batch);
+        if (!r.state || r.app_k) return QUEST_EUNSUPPORTED;  // (with an append: the caller issues it as its own launch)
+        r.kv.page_budget = 0;
+        return decode_entry(h, r, s);
     }
-    DecodeParams p{};
-    p.q = (const half_t*)q;
-    p.o = (half_t*)o;
-    p.lse = lse;
-    p.kv = (const half_t*)kv.data;
-    p.indices = kv.indices;
-    p.ws = h->ws;
-    p.st = pool_strides(kv);
-    p.n_sel = h->n_sel;
-    p.last_page_len = kv.last_page_len;
-    p.last_page_idx = kv.last_page_idx;
-    p.page_size = kv.page_size;
-    p.group = num_qo_heads / kv.num_heads;
-    p.pages_per_chunk = h->shared_ppc;
-    p.n_chunks = h->shared_chunks;
-    p.scale_log2 = (float)(1.4426950408889634 / sqrt((double)kv.head_dim));
-    p.ws_stride = h->ws_stride;
-    p.state = state;
-    p.table_stride = batch.kv_table_stride;
-    if (app.k) {
-        const quest_paged_kv_t& m = *app.metadata;
-        if (!app.v || !m.data) return QUEST_EINVAL;
+    DecodeParams p = base_params(h, r, h->shared_ppc, h->shared_chunks);
+    if (r.app_k) {
+        const quest_paged_kv_t& m = r.metadata;
+        if (!r.app_v || !m.data) return QUEST_EINVAL;
         // the append addresses the metadata pool with the KV pool's strides: same geometry required (it is: the
         // controller builds both from one KvCache class with the same page size, heads, dim and layout)
-        if (m.layout != kv.layout || m.head_dim != kv.head_dim || m.page_size != kv.page_size || m.num_heads != kv.num_heads)
-            return QUEST_EINVAL;
-        if (!state && (m.last_page_len == 0 || m.last_page_len > m.page_size)) return QUEST_EINVAL;
-        p.app_k = (const half_t*)app.k;
-        p.app_v = (const half_t*)app.v;
-        p.app_meta = (half_t*)m.data;
-        p.meta_last_page_len = m.last_page_len;
-        p.meta_last_page_idx = m.last_page_idx;
+        if (!same_pool_geometry(m, kv)) return QUEST_EINVAL;
+        if (!r.state && (m.last_page_len == 0 || m.last_page_len > m.page_size)) return QUEST_EINVAL;
+        p.app_k = (const half_t*)r.app_k, p.app_v = (const half_t*)r.app_v, p.app_meta = (half_t*)m.data;
+        p.meta_last_page_len = m.last_page_len, p.meta_last_page_idx = m.last_page_idx;
     }
-    hipStream_t s = (hipStream_t)stream;
-    return kv.head_dim == 64 ? launch_shared<64>(h, p, num_qo_heads, p.group, s, batch.n_seqs)
-                             : launch_shared<128>(h, p, num_qo_heads, p.group, s, batch.n_seqs);
+    return kv.head_dim == 64 ? launch_shared<64>(h, p, r.num_qo_heads, p.group, s, r.batch.n_seqs)
+                             : launch_shared<128>(h, p, r.num_qo_heads, p.group, s, r.batch.n_seqs);
+}
+
+// ---- the entries: fill the request, call
+
+extern "C" int quest_decode_forward(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
+                                    uint32_t num_qo_heads, float* lse, quest_stream_t stream) {
+    return decode_entry(h, attention_request(q, o, kv, num_qo_heads, lse), (hipStream_t)stream);
 }
 
 extern "C" int quest_decode_forward_shared(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
                                            uint32_t num_qo_heads, float* lse, quest_stream_t stream) {
-    return shared_entry(h, q, o, kv, num_qo_heads, lse, nullptr, stream);
+    return shared_entry(h, attention_request(q, o, kv, num_qo_heads, lse), (hipStream_t)stream);
+}
+
+extern "C" int quest_decode_forward_shared_batched(quest_decode_handler_t* h, const void* q, void* o,
+                                                   quest_paged_kv_t kv, uint32_t num_qo_heads,
+                                                   const quest_step_state_t* state, quest_batch_t batch, float* lse,
+                                                   quest_stream_t stream) {
+    if (!state) return QUEST_EINVAL;
+    if (h && batch.n_seqs > 1 && batch.kv_table_stride < h->n_sel + 1) return QUEST_EINVAL;
+    DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
+    r.state = state, r.batch = batch;
+    return shared_entry(h, r, (hipStream_t)stream);
 }
 
 extern "C" int quest_decode_forward_shared_dyn(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
                                                uint32_t num_qo_heads, const quest_step_state_t* state, float* lse,
                                                quest_stream_t stream) {
-    if (!state) return QUEST_EINVAL;
-    return shared_entry(h, q, o, kv, num_qo_heads, lse, state, stream);
-}
-
-extern "C" int quest_decode_append_forward_shared_dyn(quest_decode_handler_t* h, const void* k, const void* v,
-                                                      quest_paged_kv_t metadata, const void* q, void* o, quest_paged_kv_t kv,
-                                                      uint32_t num_qo_heads, const quest_step_state_t* state, float* lse,
-                                                      quest_stream_t stream) {
-    if (!state || !k || !v) return QUEST_EINVAL;
-    SharedAppend app;
-    app.k = k, app.v = v, app.metadata = &metadata;
-    return shared_entry(h, q, o, kv, num_qo_heads, lse, state, stream, {1, 0, 0, 0}, app);
+    return quest_decode_forward_shared_batched(h, q, o, kv, num_qo_heads, state, {1, 0, 0, 0}, lse, stream);
 }
 
 extern "C" int quest_decode_append_forward_shared_batched(quest_decode_handler_t* h, const void* k, const void* v,
@@ -1030,9 +664,17 @@ extern "C" int quest_decode_append_forward_shared_batched(quest_decode_handler_t
                                                           quest_stream_t stream) {
     if (!state || !k || !v) return QUEST_EINVAL;
     if (h && batch.n_seqs > 1 && batch.kv_table_stride < h->n_sel + 1) return QUEST_EINVAL;
-    SharedAppend app;
-    app.k = k, app.v = v, app.metadata = &metadata;
-    return shared_entry(h, q, o, kv, num_qo_heads, lse, state, stream, batch, app);
+    DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
+    r.state = state, r.batch = batch;
+    r.app_k = k, r.app_v = v, r.metadata = metadata;
+    return shared_entry(h, r, (hipStream_t)stream);
+}
+
+extern "C" int quest_decode_append_forward_shared_dyn(quest_decode_handler_t* h, const void* k, const void* v,
+                                                      quest_paged_kv_t metadata, const void* q, void* o, quest_paged_kv_t kv,
+                                                      uint32_t num_qo_heads, const quest_step_state_t* state, float* lse,
+                                                      quest_stream_t stream) {
+    return quest_decode_append_forward_shared_batched(h, k, v, metadata, q, o, kv, num_qo_heads, state, {1, 0, 0, 0}, lse, stream);
 }
 
 extern "C" int quest_decode_forward_fused_topk_strided(quest_decode_handler_t* h, const void* q, void* o,
@@ -1040,8 +682,10 @@ extern "C" int quest_decode_forward_fused_topk_strided(quest_decode_handler_t* h
                                                        uint32_t n_scores, uint32_t score_stride, void* topk_val_out,
                                                        int32_t* topk_idx_out, float* lse, quest_stream_t stream) {
     if (!scores || (score_stride != 0 && score_stride < n_scores)) return QUEST_EINVAL;
-    return decode_entry(h, q, o, kv, num_qo_heads, scores, n_scores, topk_val_out, topk_idx_out, lse,
-                        (hipStream_t)stream, score_stride);
+    DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
+    r.scores = scores, r.n_scores = n_scores, r.score_stride = score_stride;
+    r.topk_val_out = topk_val_out, r.topk_idx_out = topk_idx_out;
+    return decode_entry(h, r, (hipStream_t)stream);
 }
 
 extern "C" int quest_decode_forward_fused_topk(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
@@ -1052,24 +696,15 @@ extern "C" int quest_decode_forward_fused_topk(quest_decode_handler_t* h, const 
                                                    topk_idx_out, lse, stream);
 }
 
-extern "C" int quest_decode_forward_fused_topk_dyn(quest_decode_handler_t* h, const void* q, void* o,
-                                                   quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
-                                                   uint32_t score_stride, uint32_t max_n_scores,
-                                                   const quest_step_state_t* state, float* lse, quest_stream_t stream) {
-    if (!scores || !state || score_stride < max_n_scores) return QUEST_EINVAL;
-    // dispatch (keys per thread) is chosen for the longest row the graph will see
-    return decode_entry(h, q, o, kv, num_qo_heads, scores, max_n_scores, nullptr, nullptr, lse, (hipStream_t)stream,
-                        score_stride, state);
-}
-
-extern "C" int quest_decode_forward_fused_topk_tiles_dyn(quest_decode_handler_t* h, const void* q, void* o,
-                                                         quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
-                                                         uint32_t score_stride, uint32_t max_n_scores,
-                                                         uint32_t tile_max_offset, const quest_step_state_t* state, float* lse,
-                                                         quest_stream_t stream) {
-    if (!scores || !state || score_stride < max_n_scores || tile_max_offset == 0) return QUEST_EINVAL;
-    return decode_entry(h, q, o, kv, num_qo_heads, scores, max_n_scores, nullptr, nullptr, lse, (hipStream_t)stream,
-                        score_stride, state, {1, 0, 0, 0}, tile_max_offset);
+// The state-driven fused launches: whole rows (tile_max_offset 0) or rows that carry their tile maxima at
+// `tile_max_offset`, one sequence or a batch (blockIdx.z = sequence; live lengths and budgets per sequence).  Dispatch
+// (keys per thread) is chosen for the longest row the graph will see.
+static int fused_topk_state(quest_decode_handler* h, DecodeRequest r, const void* scores, uint32_t score_stride,
+                            uint32_t max_n_scores, uint32_t tile_max_offset, hipStream_t s) {
+    if (!scores || !r.state || score_stride < max_n_scores) return QUEST_EINVAL;
+    if (r.batch.n_seqs > 1 && r.batch.kv_table_stride < max_n_scores + 1) return QUEST_EINVAL;
+    r.scores = scores, r.n_scores = max_n_scores, r.score_stride = score_stride, r.tile_off = tile_max_offset;
+    return decode_entry(h, r, s);
 }
 
 extern "C" int quest_decode_forward_fused_topk_batched(quest_decode_handler_t* h, const void* q, void* o,
@@ -1077,23 +712,37 @@ extern "C" int quest_decode_forward_fused_topk_batched(quest_decode_handler_t* h
                                                        uint32_t score_stride, uint32_t max_n_scores,
                                                        const quest_step_state_t* state, quest_batch_t batch, float* lse,
                                                        quest_stream_t stream) {
-    if (!scores || !state || score_stride < max_n_scores) return QUEST_EINVAL;
-    if (batch.n_seqs > 1 && batch.kv_table_stride < max_n_scores + 1) return QUEST_EINVAL;
-    return decode_entry(h, q, o, kv, num_qo_heads, scores, max_n_scores, nullptr, nullptr, lse, (hipStream_t)stream,
-                        score_stride, state, batch);
+    DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
+    r.state = state, r.batch = batch;
+    return fused_topk_state(h, r, scores, score_stride, max_n_scores, 0, (hipStream_t)stream);
 }
 
-// The batched twin of quest_decode_forward_fused_topk_tiles_dyn (same body, blockIdx.z = sequence): every row of `scores`
-// carries its tile maxima at `tile_max_offset`; live lengths and budgets per sequence as in the whole-row batched entry.
+extern "C" int quest_decode_forward_fused_topk_dyn(quest_decode_handler_t* h, const void* q, void* o,
+                                                   quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
+                                                   uint32_t score_stride, uint32_t max_n_scores,
+                                                   const quest_step_state_t* state, float* lse, quest_stream_t stream) {
+    return quest_decode_forward_fused_topk_batched(h, q, o, kv, num_qo_heads, scores, score_stride, max_n_scores, state,
+                                                   {1, 0, 0, 0}, lse, stream);
+}
+
 extern "C" int quest_decode_forward_fused_topk_tiles_batched(quest_decode_handler_t* h, const void* q, void* o,
                                                              quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
                                                              uint32_t score_stride, uint32_t max_n_scores,
                                                              uint32_t tile_max_offset, const quest_step_state_t* state,
                                                              quest_batch_t batch, float* lse, quest_stream_t stream) {
     if (!scores || !state || score_stride < max_n_scores || tile_max_offset == 0) return QUEST_EINVAL;
-    if (batch.n_seqs > 1 && batch.kv_table_stride < max_n_scores + 1) return QUEST_EINVAL;
-    return decode_entry(h, q, o, kv, num_qo_heads, scores, max_n_scores, nullptr, nullptr, lse, (hipStream_t)stream,
-                        score_stride, state, batch, tile_max_offset);
+    DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
+    r.state = state, r.batch = batch;
+    return fused_topk_state(h, r, scores, score_stride, max_n_scores, tile_max_offset, (hipStream_t)stream);
+}
+
+extern "C" int quest_decode_forward_fused_topk_tiles_dyn(quest_decode_handler_t* h, const void* q, void* o,
+                                                         quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
+                                                         uint32_t score_stride, uint32_t max_n_scores,
+                                                         uint32_t tile_max_offset, const quest_step_state_t* state, float* lse,
+                                                         quest_stream_t stream) {
+    return quest_decode_forward_fused_topk_tiles_batched(h, q, o, kv, num_qo_heads, scores, score_stride, max_n_scores,
+                                                         tile_max_offset, state, {1, 0, 0, 0}, lse, stream);
 }
 
 // append + estimate + top-k + sparse attention of one layer for a whole batch in ONE launch (layer_device.cuh).
@@ -1105,18 +754,10 @@ extern "C" int quest_decode_layer_fused_batched(quest_decode_handler_t* h, const
                                                 const quest_step_state_t* state, quest_batch_t batch, void* scores_out,
                                                 uint32_t score_stride, float* lse, quest_stream_t stream) {
     if (!h || !k || !v || !q || !o || !state || batch.n_seqs == 0 || max_n_scores == 0) return QUEST_EINVAL;
-    if (!h->started) return QUEST_ESTATE;
-    if (batch.n_seqs > h->batch) return QUEST_ESTATE;
-    kv.last_page_len = metadata.last_page_len = 1;  // placeholders; the kernel reads the real ones from `state`
-    if (int e = check_pool(kv)) return e;
-    if (int e = check_pool(metadata)) return e;
-    if (kv.layout != h->layout || kv.head_dim != h->head_dim || kv.page_size != h->page_size ||
-        kv.num_heads != h->num_kv_heads || num_qo_heads != h->num_qo_heads)
-        return QUEST_EINVAL;
-    // the append and the estimate address the metadata pool with the KV pool's strides: same geometry required
-    if (metadata.layout != kv.layout || metadata.head_dim != kv.head_dim || metadata.page_size != kv.page_size ||
-        metadata.num_heads != kv.num_heads)
-        return QUEST_EINVAL;
+    DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
+    r.state = state, r.batch = batch;
+    r.app_k = k, r.app_v = v, r.metadata = metadata;
+    if (int e = check_request(h, r, Route::kLayer)) return e;
     if (scores_out && score_stride < max_n_scores) return QUEST_EINVAL;
     if (batch.n_seqs > 1 && (batch.kv_table_stride < max_n_scores + 1 ||
                              (uint64_t)batch.meta_table_stride * metadata.page_size < max_n_scores))
@@ -1128,41 +769,25 @@ extern "C" int quest_decode_layer_fused_batched(quest_decode_handler_t* h, const
     if (kv.page_size != 16 || (kv.head_dim != 128 && kv.head_dim != 64)) return QUEST_EUNSUPPORTED;
     if (max_n_scores > FC * NT) return QUEST_EUNSUPPORTED;
     LayerParams p{};
-    p.q = (const half_t*)q;
-    p.state = state;
-    p.meta = (const half_t*)metadata.data;
-    p.meta_tables = metadata.indices;
-    p.kv_tables = kv.indices;
+    p.q = (const half_t*)q, p.k_new = (const half_t*)k, p.v_new = (const half_t*)v, p.o = (half_t*)o, p.lse = lse;
+    p.state = state, p.budgets = batch.page_budgets;
+    p.meta = (const half_t*)metadata.data, p.meta_tables = metadata.indices, p.meta_table_stride = batch.meta_table_stride;
+    p.kv = (half_t*)kv.data, p.kv_tables = kv.indices, p.kv_table_stride = batch.kv_table_stride;
+    p.st = pool_strides(kv), p.num_kv_heads = kv.num_heads;
     p.n_cap = max_n_scores;
-    p.meta_table_stride = batch.meta_table_stride;
-    p.kv_table_stride = batch.kv_table_stride;
     const uint32_t per_thread = (max_n_scores + NT - 1) / NT, r4 = (per_thread + 3) / 4 * 4;
     p.cpt = r4 <= FC ? r4 : per_thread;
     p.group = num_qo_heads / kv.num_heads;
-    {   // XCD-aware row order for GQA: one workgroup per head -> period 8 (see plan_decode)
-        static const bool xcd_group = [] { const char* e = quest_tuning_env("QUEST_XCD_GROUP"); return !e || atoi(e) != 0; }();
-        p.xcd_period = (xcd_group && p.group > 1 && num_qo_heads % 8u == 0 && (num_qo_heads / 8u) % p.group == 0) ? 8u : 1u;
-    }
-    p.k_new = (const half_t*)k;
-    p.v_new = (const half_t*)v;
-    p.kv = (half_t*)kv.data;
-    p.o = (half_t*)o;
-    p.lse = lse;
+    p.xcd_period = grid_row_order(1, num_qo_heads, p.group, nullptr);  // one workgroup per head
 #ifdef QUEST_WALLSTAMPS
     p.ws = h->ws;
 #endif
-    p.budgets = batch.page_budgets;
-    p.scores_out = (uint16_t*)scores_out;
-    p.score_stride = score_stride;
-    p.sel_val_out = (uint16_t*)h->sel_val_out;
-    p.sel_idx_out = h->sel_idx_out;
-    p.sel_stride = h->n_sel;
-    p.st = pool_strides(kv);
+    p.scores_out = (uint16_t*)scores_out, p.score_stride = score_stride;
+    p.sel_val_out = (uint16_t*)h->sel_val_out, p.sel_idx_out = h->sel_idx_out, p.sel_stride = h->n_sel;
     p.n_sel = h->n_sel;
-    p.num_kv_heads = kv.num_heads;
     p.ids_lds_offset = (uint32_t)((((size_t)max_n_scores * 2) + 15) & ~(size_t)15);
     p.ws_stride = h->ws_stride;
-    p.scale_log2 = (float)(1.4426950408889634 / sqrt((double)kv.head_dim));
+    p.scale_log2 = softmax_scale_log2(kv.head_dim);
     const size_t lds = (size_t)p.ids_lds_offset + (size_t)(max_n_scores + 1u) * 4u;
     dim3 grid(1, num_qo_heads, batch.n_seqs), block(NT);
     hipStream_t s = (hipStream_t)stream;
@@ -1182,19 +807,12 @@ extern "C" int quest_decode_forward_batched(quest_decode_handler_t* h, const voi
                                             quest_stream_t stream) {
     if (!h || !state || !indices) return QUEST_EINVAL;
     if (idx_stride < h->n_sel) return QUEST_EINVAL;  // rows must hold the plan's selected-page count
-    kv.indices = indices;        // [n_seqs][num_qo_heads][idx_stride]
-    kv.page_budget = idx_stride;  // row stride of a head's list
-    batch.kv_table_stride = num_qo_heads * idx_stride;  // entries between the sequences' index blocks
-    return decode_entry(h, q, o, kv, num_qo_heads, nullptr, 0, nullptr, nullptr, lse, (hipStream_t)stream, 0, state, batch);
-}
-
-extern "C" int quest_decode_forward_shared_batched(quest_decode_handler_t* h, const void* q, void* o,
-                                                   quest_paged_kv_t kv, uint32_t num_qo_heads,
-                                                   const quest_step_state_t* state, quest_batch_t batch, float* lse,
-                                                   quest_stream_t stream) {
-    if (!state) return QUEST_EINVAL;
-    if (h && batch.n_seqs > 1 && batch.kv_table_stride < h->n_sel + 1) return QUEST_EINVAL;
-    return shared_entry(h, q, o, kv, num_qo_heads, lse, state, stream, batch);
+    DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
+    r.kv.indices = indices;        // [n_seqs][num_qo_heads][idx_stride]
+    r.kv.page_budget = idx_stride;  // row stride of a head's list
+    r.state = state, r.batch = batch;
+    r.batch.kv_table_stride = num_qo_heads * idx_stride;  // entries between the sequences' index blocks
+    return decode_entry(h, r, (hipStream_t)stream);
 }
 
 extern "C" const char* quest_error_string(int code) {

@@ -1,6 +1,6 @@
 // Block-wide deterministic top-k SELECTION over one row of 16-bit order-preserving keys held in
 // registers.  Shared by the stand-alone top-k kernel (topk.hip) and by the sparse attention kernel's
-// fused front end (sparse_attn.hip), so both produce bit-identical selections.
+// fused front end (decode_device.cuh), so both produce bit-identical selections.
 //
 // Contract (the build's declared tie rule, SURVEY.md 8a T-tie, oracle qo_topk_row): select every key
 // above the threshold key T, plus the `need` LOWEST columns among keys equal to T; a selected column's

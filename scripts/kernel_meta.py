@@ -3,13 +3,24 @@
 of the mangled name (template arguments read ILi128ELi16E...).
 
     python scripts/kernel_meta.py [substring ...]          (QUEST_HIP_LIB=<path> inspects another build)
+    python scripts/kernel_meta.py --same-code OTHER.so     is every kernel's machine code (name, size, sha256) the same?
 """
 import os
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from quest_amd.build import LIB, kernel_metadata  # noqa: E402
+from quest_amd.build import LIB, kernel_code_hashes, kernel_metadata, library_hash  # noqa: E402
+
+if sys.argv[1:2] == ["--same-code"]:
+    mine, other = os.environ.get("QUEST_HIP_LIB") or LIB, sys.argv[2]
+    a, b = kernel_code_hashes(mine), kernel_code_hashes(other)
+    diff = sorted(n for n in set(a) | set(b) if a.get(n) != b.get(n))
+    print(f"{len(a)} kernels (src {library_hash(mine)}) vs {len(b)} (src {library_hash(other)}): "
+          + ("all equal" if not diff else f"{len(diff)} differ"))
+    for n in diff:
+        print(f"  {n[:100]} {a.get(n, ('-', '-'))[0]} {b.get(n, ('-', '-'))[0]}")
+    sys.exit(1 if diff else 0)
 
 meta = kernel_metadata(os.environ.get("QUEST_HIP_LIB") or LIB)
 for name in sorted(meta):

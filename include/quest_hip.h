@@ -9,8 +9,22 @@
  * the reference side.
  *
  * Conventions
- *   - All tensors are fp16 (the reference dispatches only Half: pytorch_extension_utils.h:25-36),
- *     contiguous, resident in device memory.  Index tensors are int32.
+ *   - Tensors are contiguous and resident in device memory.  Index tensors are int32.
+ *   - Element type: fp16 (QUEST_DTYPE_F16 = 0, the default; the reference dispatches only Half:
+ *     pytorch_extension_utils.h:25-36) or bfloat16 (QUEST_DTYPE_BF16 = 1, EXTENSION).  Where this file says "fp16" of a
+ *     q / k / v / o / score tensor or a pool, read "the call's element type".  A call's element type is the `dtype` field
+ *     of the pool view(s) it is given (quest_paged_kv_t; the field was `reserved`, so a zero-initialised view still means
+ *     fp16): q, k, v, o and the score rows of that call have that type.  An unknown value, or two views of one call with
+ *     different values, is QUEST_EINVAL before anything is launched.  A decode handler has a type of its own
+ *     (quest_decode_set_dtype, default fp16) and refuses views of the other one with QUEST_EINVAL.  The two operators
+ *     that take neither a view nor a handler have one typed entry each: quest_apply_rope_in_place_dtype (all four RoPE
+ *     forms) and quest_rms_norm_forward_dtype; every other symbol keeps its signature and, given zeroed views, its fp16
+ *     meaning.  Top-k (quest_topk_filtering*) orders 16-bit sign-magnitude bit patterns and is the same code for both.
+ *     bf16 differences: metadata max / min treat patterns above 0x7f80 as NaN, a new page's entry starts from -/+ the
+ *     largest finite bf16 (0xff7f / 0x7f7f) instead of -/+65504, scores are bf16_rne of the same fp32 sum, partial
+ *     attention states stay fp32.  fp16 only: the decode-layer projections (quest_decode_norm_gemv, _gemv_residual,
+ *     _mlp_gate_up, _qkv_rope*) and quest_decode_layer_fused_batched, which returns QUEST_EUNSUPPORTED for bf16 views
+ *     (the caller issues quest_append_estimate_batched + quest_decode_forward_fused_topk_batched).
  *   - Return value: 0 on success; a positive value is a hipError_t from a launch; a negative
  *     value is one of the QUEST_E* argument errors below.  quest_error_string() names both.
  *     Nothing throws; nothing allocates except quest_decode_begin_forward (workspace, like
@@ -48,6 +62,10 @@ typedef void* quest_stream_t; /* hipStream_t */
  */
 #define QUEST_LAYOUT_NHD_ROT 2u
 
+/* Element type of a pool and of the q / k / v / o / score tensors that travel with it (quest_paged_kv_t.dtype). */
+#define QUEST_DTYPE_F16 0u
+#define QUEST_DTYPE_BF16 1u
+
 #define QUEST_EINVAL (-1)      /* malformed argument (null pointer, zero size, bad layout) */
 #define QUEST_EUNSUPPORTED (-2) /* head_dim / page_size / group size outside the built set */
 #define QUEST_ESTATE (-3)      /* forward without begin_forward (decode_handler.cuh:226-231) */
@@ -61,7 +79,7 @@ typedef void* quest_stream_t; /* hipStream_t */
  * passes to its kernels by value; so is this.
  */
 typedef struct quest_paged_kv {
-    void* data;             /* fp16 pool base of this layer (kv_cache.py:111-113 buf_layer) */
+    void* data;             /* pool base of this layer, elements of type `dtype` (kv_cache.py:111-113 buf_layer) */
     const int32_t* indices; /* page table; for quest_decode_forward: [num_qo_heads][page_budget] */
     const int32_t* indptr;  /* device int32[2] = {0, n_pages} */
     uint32_t num_heads;     /* heads stored in the pool (kv heads) */
@@ -71,7 +89,7 @@ typedef struct quest_paged_kv {
     uint32_t last_page_len; /* 1..page_size */
     int32_t last_page_idx;  /* physical id of the sequence's last page */
     uint32_t layout;
-    uint32_t reserved;
+    uint32_t dtype;         /* QUEST_DTYPE_F16 (0: what a zero-initialised view means) or QUEST_DTYPE_BF16 */
 } quest_paged_kv_t;
 
 /* Where a vector lives inside an entry's row of heads (host function, no GPU): the head SLOT of head `head`'s K / max vector
@@ -428,6 +446,10 @@ int quest_decode_forward_batched(quest_decode_handler_t* h, const void* q, void*
 int quest_apply_rope_in_place_batched(void* q, void* k, uint32_t num_qo_heads, uint32_t num_kv_heads,
                                       uint32_t head_dim, float rope_scale, float rope_theta,
                                       const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream);
+/* Element type of the pools / q / o this handler's forwards serve (QUEST_DTYPE_*; default QUEST_DTYPE_F16).  Every forward
+ * checks its view's dtype against it (QUEST_EINVAL).  May be called at any time between forwards; the plan and the fp32
+ * workspace do not depend on it.  QUEST_EINVAL for an unknown value. */
+int quest_decode_set_dtype(quest_decode_handler_t* h, uint32_t dtype);
 /* Sequences per launch the next begin_forward plans (workspace, work split) for; default 1. */
 int quest_decode_set_batch(quest_decode_handler_t* h, uint32_t n_seqs);
 
@@ -486,9 +508,21 @@ int quest_apply_rope_in_place_freqs(void* q, void* k, uint32_t n, uint32_t past_
                                     uint32_t num_kv_heads, uint32_t head_dim, const float* inv_freq,
                                     float attention_factor, const quest_step_state_t* states, quest_stream_t stream);
 
+/* The RoPE entries above for q / k of element type `dtype` (QUEST_DTYPE_*), in one entry: inv_freq NULL = the
+ * rope_scale / rope_theta formula of quest_apply_rope_in_place (attention_factor unused), else the table form of
+ * quest_apply_rope_in_place_freqs (rope_scale / rope_theta unused); states NULL = rows at past_kv_len + i, else row i at
+ * states[i].seq_len - 1 (n = sequences).  fp32 arithmetic, one rounding to the element type. */
+int quest_apply_rope_in_place_dtype(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
+                                    uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
+                                    const float* inv_freq, float attention_factor, const quest_step_state_t* states,
+                                    uint32_t dtype, quest_stream_t stream);
+
 /* rms_norm_forward (bsk_ops.h:29-32, rms_norm.cu:160-212). input/output: [rows][cols], weight [cols]. */
 int quest_rms_norm_forward(const void* input, const void* weight, void* output, uint32_t rows,
                            uint32_t cols, float epsilon, quest_stream_t stream);
+/* The same for input / weight / output of element type `dtype` (QUEST_DTYPE_*). */
+int quest_rms_norm_forward_dtype(const void* input, const void* weight, void* output, uint32_t rows, uint32_t cols,
+                                 float epsilon, uint32_t dtype, quest_stream_t stream);
 
 /*
  * prefill_with_paged_kv_cache (bsk_ops.h:78-86, batch_prefill.cu:27-117 -> BatchPrefillWithPagedKVCache,

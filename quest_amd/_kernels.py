@@ -68,8 +68,24 @@ def _check_ge(a, b, what: str) -> None:
         raise RuntimeError(f"CHECK_GE({what}) failed. {a} vs {b}")
 
 
-def _check_half(x: torch.Tensor, op: str) -> None:
-    if x.dtype != torch.float16:  # DISPATCH_PYTORCH_DTYPE_TO_CTYPE has only Half
+# torch dtype -> QUEST_DTYPE_* (include/quest_hip.h).  The reference's DISPATCH_PYTORCH_DTYPE_TO_CTYPE has only Half;
+# bfloat16 is this library's second element type.  Anything else (float32, ...) has no kernel.
+_DTYPES = {torch.float16: 0, torch.bfloat16: 1}
+
+
+def _check_half(x: torch.Tensor, op: str, *same) -> None:
+    """``x`` is fp16 or bf16 and every tensor of ``same`` (the other data tensors of the call; None entries skipped) has
+    ``x``'s dtype: one call, one element type."""
+    if x.dtype not in _DTYPES:
+        raise RuntimeError(f"{op} failed to dispatch with dtype {x.dtype}")
+    for t in same:
+        if t is not None and t.dtype != x.dtype:
+            raise RuntimeError(f"{op} failed to dispatch with dtype {t.dtype} (the call's other tensors are {x.dtype})")
+
+
+def _check_f16(x: torch.Tensor, op: str) -> None:
+    """The fp16-only operators (the decode-layer projections of csrc/decode_layer.hip)."""
+    if x.dtype != torch.float16:
         raise RuntimeError(f"{op} failed to dispatch with dtype {x.dtype}")
 
 
@@ -101,11 +117,14 @@ def _pool_dims(data: torch.Tensor, layout: int):
 
 def _paged(data, indices, indptr, last_page_len, last_page_idx, layout, page_budget=0) -> PagedKV:
     page_size, num_heads, head_dim = _pool_dims(data, layout)
+    if data.dtype not in _DTYPES:
+        raise RuntimeError(f"paged pool failed to dispatch with dtype {data.dtype}")
     return PagedKV(
         data.data_ptr(),
         indices.data_ptr() if indices is not None else None,
         indptr.data_ptr() if indptr is not None else None,
-        num_heads, page_size, head_dim, page_budget, int(last_page_len), int(last_page_idx), int(layout), 0)
+        num_heads, page_size, head_dim, page_budget, int(last_page_len), int(last_page_idx), int(layout),
+        _DTYPES[data.dtype])  # the view carries the element type of the call (quest_paged_kv_t.dtype)
 
 
 # ---------------------------------------------------------------- free functions
@@ -118,10 +137,22 @@ def apply_rope_in_place(q, k, past_kv_len: int, rope_scale: float, rope_theta: f
     _check_dim(3, k, "k")
     _check_eq(q.size(0), k.size(0), "q.size(0), k.size(0)")
     _check_eq(q.size(2), k.size(2), "q.size(2), k.size(2)")
-    _check_half(q, "apply_rope_in_place")
+    _check_half(q, "apply_rope_in_place", k)
+    if q.dtype != torch.float16:
+        return _rope_typed(q, k, q.size(0), past_kv_len, rope_scale, rope_theta, None, 1.0, None, "apply_rope_in_place")
     check(lib.quest_apply_rope_in_place(q.data_ptr(), k.data_ptr(), q.size(0), int(past_kv_len), q.size(1),
                                         k.size(1), q.size(2), float(rope_scale), float(rope_theta), _stream(q)),
           "apply_rope_in_place")
+
+
+def _rope_typed(q, k, n: int, past_kv_len: int, rope_scale: float, rope_theta: float, inv_freq, attention_factor: float,
+                states, what: str) -> None:
+    """The RoPE forms for q / k that are not fp16: the one typed entry of the C ABI (quest_apply_rope_in_place_dtype)."""
+    check(lib.quest_apply_rope_in_place_dtype(q.data_ptr(), k.data_ptr(), int(n), int(past_kv_len), q.size(1), k.size(1),
+                                              q.size(2), float(rope_scale), float(rope_theta),
+                                              inv_freq.data_ptr() if inv_freq is not None else None,
+                                              float(attention_factor), states.data_ptr() if states is not None else None,
+                                              _DTYPES[q.dtype], _stream(q)), what)
 
 
 def _check_rope_table(inv_freq, head_dim: int) -> None:
@@ -143,12 +174,14 @@ def apply_rope_in_place_freqs(q, k, inv_freq, attention_factor: float, past_kv_l
     _check_dim(3, k, "k")
     _check_eq(q.size(0), k.size(0), "q.size(0), k.size(0)")
     _check_eq(q.size(2), k.size(2), "q.size(2), k.size(2)")
-    _check_half(q, "apply_rope_in_place")
-    _check_half(k, "apply_rope_in_place")
+    _check_half(q, "apply_rope_in_place", k)
     _check_rope_table(inv_freq, q.size(2))
     if states is not None:
         _check_input(states, "states")
         _check_eq(states.numel(), q.size(0) * STEP_STATE_INTS, "states.numel(), n * 8")
+    if q.dtype != torch.float16:
+        return _rope_typed(q, k, q.size(0), past_kv_len, 1.0, 1.0, inv_freq, attention_factor, states,
+                           "apply_rope_in_place_freqs")
     check(lib.quest_apply_rope_in_place_freqs(q.data_ptr(), k.data_ptr(), q.size(0), int(past_kv_len), q.size(1),
                                               k.size(1), q.size(2), inv_freq.data_ptr(), float(attention_factor),
                                               states.data_ptr() if states is not None else None, _stream(q)),
@@ -161,7 +194,11 @@ def rms_norm_forward(input, weight, output, epsilon: float) -> None:
     _check_input(weight, "weight")
     _check_input(output, "output")
     _check_eq(input.dim(), 3, "input.dim(), 3")
-    _check_half(input, "rms_norm_forward")
+    _check_half(input, "rms_norm_forward", weight, output)
+    if input.dtype != torch.float16:
+        return check(lib.quest_rms_norm_forward_dtype(input.data_ptr(), weight.data_ptr(), output.data_ptr(),
+                                                      input.size(0) * input.size(1), input.size(2), float(epsilon),
+                                                      _DTYPES[input.dtype], _stream(input)), "rms_norm")
     check(lib.quest_rms_norm_forward(input.data_ptr(), weight.data_ptr(), output.data_ptr(),
                                      input.size(0) * input.size(1), input.size(2), float(epsilon), _stream(input)),
           "rms_norm")
@@ -184,7 +221,7 @@ def topk_filtering(estimated_value, estimated_indices, d_out, indices_out, buf, 
     _check_eq(indices_out.dtype, torch.int32, "indices_out.scalar_type(), torch::kInt32")
     _check_eq(page_budget, d_out.size(1), "page_budget, d_out.size(1)")
     _check_eq(page_budget, indices_out.size(1), "page_budget, indices_out.size(1)")
-    _check_half(estimated_value, "Top-k filtering")
+    _check_half(estimated_value, "Top-k filtering", d_out)  # (the selection orders 16-bit patterns: one code for both types)
     check(lib.quest_topk_filtering_strided(estimated_value.data_ptr(), estimated_value.stride(0), estimated_indices.data_ptr(),
                                            d_out.data_ptr(), indices_out.data_ptr(),
                                            buf.data_ptr() if buf is not None else None, num_heads, num_pages,
@@ -205,7 +242,7 @@ def estimate_attn_score(q, o, metadata_data, metadata_indices, metadata_indptr, 
     _check_dim(1, metadata_indices, "metadata_indices")
     _check_eq(q.size(0), 1, "q.size(0), 1")
     _check_eq(metadata_indices.dtype, torch.int32, "metadata_indices.scalar_type(), torch::kInt32")
-    _check_half(q, "Estimate_attn_score")
+    _check_half(q, "Estimate_attn_score", o, metadata_data)
     page_size, num_kv_heads, head_dim = _pool_dims(metadata_data, layout)
     _check_eq(metadata_data.size(4), q.size(2), "metadata_data.size(4), head_dim")
     _check_eq(o.size(0), q.size(1), "o.size(0), num_heads")
@@ -240,7 +277,7 @@ def append_kv_cache_prefill(k, v, kv_data, kv_indices, kv_indptr, kv_last_page_l
     """page.cu:101-210.  k, v ``[N>=2, H, D]`` appended; per-page min/max metadata rebuilt."""
     _check_append(k, v, kv_data, kv_indices, kv_indptr, metadata_data, metadata_indices, metadata_indptr, layout)
     _check_ge(k.size(0), 2, "k.size(0), 2")
-    _check_half(k, "Append_kv_cache_prefill")
+    _check_half(k, "Append_kv_cache_prefill", v, kv_data, metadata_data)
     kv = _paged(kv_data, kv_indices, kv_indptr, kv_last_page_len, kv_last_page_idx, layout)
     meta = _paged(metadata_data, metadata_indices, metadata_indptr, metadata_last_page_len, metadata_last_page_idx,
                   layout)
@@ -254,7 +291,7 @@ def append_kv_cache_decode(k, v, kv_data, kv_indices, kv_indptr, kv_last_page_le
     """page.cu:6-99.  k, v ``[1, H, D]``."""
     _check_append(k, v, kv_data, kv_indices, kv_indptr, metadata_data, metadata_indices, metadata_indptr, layout)
     _check_eq(k.size(0), 1, "k.size(0), 1")
-    _check_half(k, "Append_kv_cache_decode")
+    _check_half(k, "Append_kv_cache_decode", v, kv_data, metadata_data)
     kv = _paged(kv_data, kv_indices, kv_indptr, kv_last_page_len, kv_last_page_idx, layout)
     meta = _paged(metadata_data, metadata_indices, metadata_indptr, metadata_last_page_len, metadata_last_page_idx,
                   layout)
@@ -274,8 +311,8 @@ def append_estimate(k, v, kv_data, kv_indices, kv_indptr, kv_last_page_len: int,
     _check_dim(3, q, "q")
     _check_eq(q.size(0), 1, "q.size(0), 1")
     _check_eq(o.size(0), q.size(1), "o.size(0), num_heads")
-    _check_half(k, "Append_kv_cache_decode")
-    _check_half(q, "Estimate_attn_score")
+    _check_half(k, "Append_kv_cache_decode", v, kv_data, metadata_data)
+    _check_half(q, "Estimate_attn_score", o, k)
     kv = _paged(kv_data, kv_indices, kv_indptr, kv_last_page_len, kv_last_page_idx, layout)
     meta = _paged(metadata_data, metadata_indices, metadata_indptr, metadata_last_page_len, metadata_last_page_idx,
                   layout)
@@ -288,20 +325,20 @@ def append_estimate(k, v, kv_data, kv_indices, kv_indptr, kv_last_page_len: int,
 def _check_vec(x, n: int, name: str) -> None:
     _check_input(x, name)
     _check_eq(x.numel(), n, f"{name}.numel(), {n}")
-    _check_half(x, name)
+    _check_f16(x, name)
 
 
 def _check_mat(x, n: int, cols: int, name: str) -> None:
     _check_input(x, name)
     _check_eq(x.numel(), n * cols, f"{name}.numel(), {n} * {cols}")
-    _check_half(x, name)
+    _check_f16(x, name)
 
 
 def _check_weight(w, out_dim: int, in_dim: int, name: str) -> None:
     _check_input(w, name)
     _check_dim(2, w, name)
     _check_eq(tuple(w.shape), (out_dim, in_dim), f"{name}.shape, (out, in)")
-    _check_half(w, name)
+    _check_f16(w, name)
 
 
 def decode_norm_gemv(x, gamma, eps: float, w, out) -> None:
@@ -529,8 +566,8 @@ def append_estimate_batched(k, v, kv_data, kv_tables, q, o, metadata_data, meta_
     _check_eq(o.size(0), b.n_seqs, "o.size(0), n_seqs")
     _check_eq(o.size(1), q.size(1), "o.size(1), num_heads")
     _check_ge(o.size(2), max_n_out, "o.size(2), max_n_out")
-    _check_half(k, "Append_kv_cache_decode")
-    _check_half(q, "Estimate_attn_score")
+    _check_half(k, "Append_kv_cache_decode", v, kv_data, metadata_data)
+    _check_half(q, "Estimate_attn_score", o, k)
     kv = _paged(kv_data, kv_tables, None, 1, 0, layout)
     meta = _paged(metadata_data, meta_tables, None, 1, 0, layout)
     if tiles:
@@ -562,7 +599,7 @@ def estimate_attn_score_batched(q, o, metadata_data, meta_tables, state, max_n_o
     _check_eq(o.size(0), b.n_seqs, "o.size(0), n_seqs")
     _check_eq(o.size(1), q.size(1), "o.size(1), num_heads")
     _check_ge(o.size(2), max_n_out, "o.size(2), max_n_out")
-    _check_half(q, "Estimate_attn_score")
+    _check_half(q, "Estimate_attn_score", o, metadata_data)
     meta = _paged(metadata_data, meta_tables, None, 1, 0, layout)
     check(lib.quest_estimate_attn_score_batched(q.data_ptr(), o.data_ptr(), q.size(1), o.size(2), int(max_n_out), meta,
                                                 state.data_ptr(), b, _stream(q)), "Estimate_attn_score")
@@ -585,7 +622,7 @@ def topk_filtering_batched(scores, kv_tables, d_out, indices_out, state, max_num
     _check_eq(tuple(indices_out.shape), tuple(d_out.shape), "indices_out.shape, d_out.shape")
     _check_eq(indices_out.dtype, torch.int32, "indices_out.scalar_type(), torch::kInt32")
     _check_ge(scores.size(2), max_num_pages, "scores.size(2), max_num_pages")
-    _check_half(scores, "Top-k filtering")
+    _check_half(scores, "Top-k filtering", d_out)
     check(lib.quest_topk_filtering_batched(scores.data_ptr(), scores.size(2), int(max_num_pages), kv_tables.data_ptr(),
                                            d_out.data_ptr(), indices_out.data_ptr(), d_out.size(2), scores.size(1),
                                            int(page_budget), state.data_ptr(), b, _stream(scores)), "Top-k filtering")
@@ -597,7 +634,7 @@ def append_kv_cache_decode_batched(k, v, kv_data, kv_tables, metadata_data, meta
         _check_input(t, n)
     b = _batch(state, kv_tables, meta_tables)
     _check_eq(k.size(0), b.n_seqs, "k.size(0), n_seqs")
-    _check_half(k, "Append_kv_cache_decode")
+    _check_half(k, "Append_kv_cache_decode", v, kv_data, metadata_data)
     kv = _paged(kv_data, kv_tables, None, 1, 0, layout)
     meta = _paged(metadata_data, meta_tables, None, 1, 0, layout)
     check(lib.quest_append_kv_cache_decode_batched(k.data_ptr(), v.data_ptr(), kv, meta, state.data_ptr(), b,
@@ -612,7 +649,9 @@ def apply_rope_in_place_batched(q, k, rope_scale: float, rope_theta: float, stat
     b = _batch(state, None, None)
     _check_eq(q.size(0), b.n_seqs, "q.size(0), n_seqs")
     _check_eq(k.size(0), b.n_seqs, "k.size(0), n_seqs")
-    _check_half(q, "apply_rope_in_place")
+    _check_half(q, "apply_rope_in_place", k)
+    if q.dtype != torch.float16:
+        return _rope_typed(q, k, b.n_seqs, 0, rope_scale, rope_theta, None, 1.0, state, "apply_rope_in_place_batched")
     check(lib.quest_apply_rope_in_place_batched(q.data_ptr(), k.data_ptr(), q.size(1), k.size(1), q.size(2),
                                                 float(rope_scale), float(rope_theta), state.data_ptr(), b,
                                                 _stream(q)), "apply_rope_in_place_batched")
@@ -635,7 +674,7 @@ def prefill_with_paged_kv_cache(q, kv_data, kv_indices, kv_last_page_len: int, c
     _check_dim(1, kv_indices, "kv_indices")
     _check_eq(kv_indices.dtype, torch.int32, "kv_indices.scalar_type(), torch::kInt32")
     _check_eq(q.size(2), kv_data.size(4), "q.size(2), kv_data.size(4)")
-    _check_half(q, "BatchPrefillWithPagedKVCache")
+    _check_half(q, "BatchPrefillWithPagedKVCache", kv_data)
     o = torch.empty_like(q)
     if q.size(0) == 0:  # nothing to attend from (the reference launches an empty grid)
         return o
@@ -650,11 +689,19 @@ def prefill_with_paged_kv_cache(q, kv_data, kv_indices, kv_last_page_len: int, c
 class BatchDecodeWithPagedKVCachePyTorchWrapper:
     """bsk_ops.h:88-117 / approx_attn.cu:27-150: begin_forward plans, forward launches."""
 
-    def __init__(self, layout: int):
+    def __init__(self, layout: int, *, dtype: torch.dtype = torch.float16):
+        """``dtype`` (EXTENSION, keyword only): the element type this handler serves.  Constructed the reference's way it
+        is fp16 and refuses everything else, like the reference's dispatch; ``dtype=torch.bfloat16`` makes a bf16 handler
+        (which refuses fp16).  float32 has no kernels."""
         self._layout = int(layout)
+        if dtype not in _DTYPES:
+            raise RuntimeError(f"BatchDecodeWithPagedKVCache failed to dispatch with dtype {dtype}")
+        self._dtype = dtype
         h = ctypes.c_void_p()
         check(lib.quest_decode_handler_create(ctypes.byref(h), self._layout), "BatchDecodeWithPagedKVCache")
         self._h = h
+        if dtype != torch.float16:
+            check(lib.quest_decode_set_dtype(h, _DTYPES[dtype]), "BatchDecodeWithPagedKVCache")
         self._destroy = lib.quest_decode_handler_destroy  # keep alive for __del__ at interpreter exit
 
     def __del__(self):
@@ -666,7 +713,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
                       empty_data) -> None:
         _check_dim(1, indptr, "indptr")
         _check_eq(indptr.dtype, torch.int32, "indptr.scalar_type(), torch::kInt32")
-        if empty_data.dtype != torch.float16:
+        if empty_data.dtype != self._dtype:
             raise RuntimeError(f"BatchDecodeWithPagedKVCache failed to dispatch with dtype {empty_data.dtype}")
         # the planner needs the selected-page count on the host; the reference copies indptr back
         # too (decode_attn.cuh:866-873).  A CPU indptr skips the device sync.
@@ -675,6 +722,13 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         stream = torch.cuda.current_stream().cuda_stream if torch.cuda.is_available() else None
         check(lib.quest_decode_begin_forward(self._h, n_sel, int(num_qo_heads), int(num_kv_heads), int(head_dim),
                                              int(page_size), stream), "BatchDecodeWithPagedKVCache")
+
+    def _check_dtype(self, q, *same) -> None:
+        """q has the handler's element type and so have the call's other data tensors."""
+        if q.dtype != self._dtype:
+            raise RuntimeError(f"BatchDecodeWithPagedKVCache failed to dispatch with dtype {q.dtype} "
+                               f"(the handler was made for {self._dtype})")
+        _check_half(q, "BatchDecodeWithPagedKVCache", *same)
 
     def end_forward(self) -> None:
         check(lib.quest_decode_end_forward(self._h), "BatchDecodeWithPagedKVCache")
@@ -692,7 +746,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_eq(paged_kv_data.size(1), 2, "paged_kv_data.size(1), 2")
         _check_eq(paged_kv_data.size(4), q.size(2), "paged_kv_data.size(4), head_dim")
         _check_eq(paged_kv_indices.dtype, torch.int32, "paged_kv_indices.scalar_type(), torch::kInt32")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
+        self._check_dtype(q, o, paged_kv_data)
         kv = _paged(paged_kv_data, paged_kv_indices, paged_kv_indptr, paged_kv_last_page_len,
                     paged_kv_last_page_idx, self._layout, page_budget=paged_kv_indices.size(1))
         check(lib.quest_decode_forward(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), None, _stream(q)),
@@ -709,7 +763,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_input(page_list, "page_list")
         _check_dim(1, page_list, "page_list")
         _check_eq(page_list.dtype, torch.int32, "page_list.scalar_type(), torch::kInt32")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
+        self._check_dtype(q, o, paged_kv_data)
         kv = _paged(paged_kv_data, page_list, None, paged_kv_last_page_len, paged_kv_last_page_idx, self._layout)
         return _launched(lib.quest_decode_forward_shared(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), None,
                                                          _stream(q)), "BatchDecodeWithPagedKVCache")
@@ -730,8 +784,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_eq(scores.size(0), q.size(1), "scores.size(0), num_qo_heads")
         _check_eq(page_table.size(0), scores.size(1) + 1, "page_table.size(0), n_scores + 1")
         _check_eq(page_table.dtype, torch.int32, "page_table.scalar_type(), torch::kInt32")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
-        _check_half(scores, "BatchDecodeWithPagedKVCache")
+        self._check_dtype(q, o, paged_kv_data, scores)
         kv = _paged(paged_kv_data, page_table, None, paged_kv_last_page_len, paged_kv_last_page_idx, self._layout)
         # (QUEST_EUNSUPPORTED: chunk larger than the fused front end stages)
         return _launched(lib.quest_decode_forward_fused_topk_strided(
@@ -752,7 +805,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         b = _batch(state, kv_tables, None)
         _check_dim(3, q, "q")
         _check_eq(q.size(0), b.n_seqs, "q.size(0), n_seqs")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
+        self._check_dtype(q, o, paged_kv_data)
         kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
         check(lib.quest_decode_forward_shared_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
                                                       state.data_ptr(), b, None, _stream(q)),
@@ -773,8 +826,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_dim(3, q, "q")
         _check_eq(q.size(0), b.n_seqs, "q.size(0), n_seqs")
         _check_eq(k.size(0), b.n_seqs, "k.size(0), n_seqs")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
-        _check_half(k, "BatchDecodeWithPagedKVCache")
+        self._check_dtype(q, o, paged_kv_data, k, v, metadata_data)
         _check_eq(tuple(k.shape), tuple(v.shape), "k.shape, v.shape")
         kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
         _check_eq(tuple(k.shape[-2:]), (kv.num_heads, kv.head_dim), "k.shape[-2:], (kv heads, head_dim)")
@@ -799,7 +851,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_eq(indices.size(0), b.n_seqs, "indices.size(0), n_seqs")
         _check_eq(indices.size(1), q.size(1), "indices.size(1), num_qo_heads")
         _check_eq(indices.dtype, torch.int32, "indices.scalar_type(), torch::kInt32")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
+        self._check_dtype(q, o, paged_kv_data)
         kv = _paged(paged_kv_data, None, None, 1, 0, self._layout)
         check(lib.quest_decode_forward_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), indices.data_ptr(),
                                                indices.size(2), state.data_ptr(), b, None, _stream(q)),
@@ -822,7 +874,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_eq(scores.size(0), b.n_seqs, "scores.size(0), n_seqs")
         _check_eq(scores.size(1), q.size(1), "scores.size(1), num_qo_heads")
         _check_ge(scores.size(2), max_n_scores, "scores.size(2), max_n_scores")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
+        self._check_dtype(q, o, paged_kv_data, scores)  # (the score rows are read as 16-bit keys of the handler's type)
         kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
         if tiles:
             _check_ge(scores.size(2), tiles_row_stride(max_n_scores), "scores.size(2), tiles_row_stride(max_n_scores)")
@@ -856,8 +908,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_eq(k.size(0), b.n_seqs, "k.size(0), n_seqs")
         _check_eq(tuple(o.shape), tuple(q.shape), "o.shape, q.shape")
         _check_eq(tuple(k.shape), tuple(v.shape), "k.shape, v.shape")
-        _check_half(q, "BatchDecodeWithPagedKVCache")
-        _check_half(k, "BatchDecodeWithPagedKVCache")
+        self._check_dtype(q, o, paged_kv_data, k, v, metadata_data)
         kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
         _check_eq(tuple(k.shape[-2:]), (kv.num_heads, kv.head_dim), "k.shape[-2:], (kv heads, head_dim)")
         meta = _paged(metadata_data, meta_tables, None, 1, 0, self._layout)
@@ -868,7 +919,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
             _check_dim(3, scores_out, "scores_out")
             _check_eq(tuple(scores_out.shape[:2]), tuple(q.shape[:2]), "scores_out.shape[:2], (n_seqs, num_qo_heads)")
             _check_ge(scores_out.size(2), max_n_scores, "scores_out.size(2), max_n_scores")
-            _check_half(scores_out, "BatchDecodeWithPagedKVCache")
+            self._check_dtype(q, scores_out)
             sc_ptr, sc_stride = scores_out.data_ptr(), scores_out.size(2)
         return _launched(lib.quest_decode_layer_fused_batched(
             self._h, k.data_ptr(), v.data_ptr(), meta, q.data_ptr(), o.data_ptr(), kv, q.size(1), int(max_n_scores),
@@ -908,7 +959,9 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
             _check_eq(idx_out.dtype, torch.int32, "idx_out.scalar_type(), torch::kInt32")
         if val_out is not None:
             _check_input(val_out, "val_out")
-            _check_half(val_out, "set_selection_out")
+            if val_out.dtype != self._dtype:
+                raise RuntimeError(f"set_selection_out failed to dispatch with dtype {val_out.dtype} "
+                                   f"(the handler was made for {self._dtype})")
         self._sel_keepalive = (val_out, idx_out)
         check(lib.quest_decode_set_selection_out(self._h, val_out.data_ptr() if val_out is not None else None,
                                                  idx_out.data_ptr() if idx_out is not None else None),

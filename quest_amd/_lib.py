@@ -28,7 +28,7 @@ class PagedKV(ctypes.Structure):
         ("last_page_len", c_u32),
         ("last_page_idx", c_i32),
         ("layout", c_u32),
-        ("reserved", c_u32),
+        ("dtype", c_u32),  # QUEST_DTYPE_F16 (0) / QUEST_DTYPE_BF16 (1)
     ]
 
 
@@ -98,6 +98,10 @@ SIGNATURES = {
                                                      c_vp]),
     "quest_decode_forward_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_vp, Batch, c_vp, c_vp]),
     "quest_decode_set_batch": (ctypes.c_int, [c_vp, c_u32]),
+    "quest_decode_set_dtype": (ctypes.c_int, [c_vp, c_u32]),
+    "quest_apply_rope_in_place_dtype": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_u32, c_f32, c_f32, c_vp,
+                                                        c_f32, c_vp, c_u32, c_vp]),
+    "quest_rms_norm_forward_dtype": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_u32, c_vp]),
     "quest_decode_plan_info": (ctypes.c_int, [c_vp, ctypes.POINTER(c_u32), ctypes.POINTER(c_u32)]),
     "quest_decode_debug_workspace": (ctypes.c_int, [c_vp, ctypes.POINTER(c_vp), ctypes.POINTER(ctypes.c_uint64),
                                                     ctypes.POINTER(c_u32)]),

@@ -13,10 +13,11 @@
 
 namespace quest {
 
-__global__ __launch_bounds__(256) void append_decode_kernel(quest_paged_kv_t kv, quest_paged_kv_t meta,
-                                                            const uint16_t* __restrict__ key,
-                                                            const uint16_t* __restrict__ value,
-                                                            const quest_step_state_t* state) {
+template <typename T>
+__device__ __forceinline__ void append_decode_launch_body(quest_paged_kv_t kv, quest_paged_kv_t meta,
+                                                          const uint16_t* __restrict__ key,
+                                                          const uint16_t* __restrict__ value,
+                                                          const quest_step_state_t* state) {
     if (state) {  // state-driven launch: lengths / last-page ids from device memory; blockIdx.y = sequence
         const quest_step_state_t st = state[blockIdx.y];
         key += (size_t)blockIdx.y * kv.num_heads * kv.head_dim;
@@ -26,15 +27,28 @@ __global__ __launch_bounds__(256) void append_decode_kernel(quest_paged_kv_t kv,
         meta.last_page_len = (uint32_t)st.meta_last_page_len;
         meta.last_page_idx = st.meta_last_page_idx;
     }
-    append_decode_body(kv, meta, key, value, blockIdx.x * blockDim.x + threadIdx.x);
+    append_decode_body<T>(kv, meta, key, value, blockIdx.x * blockDim.x + threadIdx.x);
+}
+// the two element types of a pool (quest_paged_kv_t.dtype) are separately named kernels over the one body
+__global__ __launch_bounds__(256) void append_decode_kernel(quest_paged_kv_t kv, quest_paged_kv_t meta,
+                                                            const uint16_t* __restrict__ key,
+                                                            const uint16_t* __restrict__ value,
+                                                            const quest_step_state_t* state) {
+    append_decode_launch_body<half_t>(kv, meta, key, value, state);
+}
+__global__ __launch_bounds__(256) void append_decode_kernel_bf16(quest_paged_kv_t kv, quest_paged_kv_t meta,
+                                                                 const uint16_t* __restrict__ key,
+                                                                 const uint16_t* __restrict__ value,
+                                                                 const quest_step_state_t* state) {
+    append_decode_launch_body<bf16_t>(kv, meta, key, value, state);
 }
 
 // One row of lanes per (page, head); rows of a wave are consecutive heads of one page so source
 // and (NHD) destination accesses are 1 KiB contiguous per wave instruction.
-__global__ __launch_bounds__(256) void append_prefill_kernel(quest_paged_kv_t kv, quest_paged_kv_t meta,
-                                                             const uint16_t* __restrict__ key,
-                                                             const uint16_t* __restrict__ value,
-                                                             uint32_t append_len) {
+template <typename T>
+__device__ __forceinline__ void append_prefill_body(const quest_paged_kv_t& kv, const quest_paged_kv_t& meta,
+                                                    const uint16_t* __restrict__ key,
+                                                    const uint16_t* __restrict__ value, uint32_t append_len) {
     const uint32_t D = kv.head_dim, H = kv.num_heads, S = kv.page_size, MS = meta.page_size;
     const uint32_t lpr = D / kVec;
     const uint32_t rows_per_block = blockDim.x / lpr;
@@ -72,8 +86,8 @@ __global__ __launch_bounds__(256) void append_prefill_kernel(quest_paged_kv_t kv
         mx = *reinterpret_cast<const ushort8*>(mmax);
         mn = *reinterpret_cast<const ushort8*>(mmin);
     } else {
-        mx = (ushort8)(kHalfNegMax);
-        mn = (ushort8)(kHalfMax);
+        mx = (ushort8)(kElemNegMax<T>);
+        mn = (ushort8)(kElemMax<T>);
     }
     const size_t src0 = ((size_t)(po * (int32_t)S - start_seq) * H + h) * D + f;
 #pragma unroll 4
@@ -81,14 +95,26 @@ __global__ __launch_bounds__(256) void append_prefill_kernel(quest_paged_kv_t kv
         const size_t src = src0 + (size_t)e * H * D;
         const ushort8 k8 = *reinterpret_cast<const ushort8*>(key + src);
         const ushort8 v8 = *reinterpret_cast<const ushort8*>(value + src);
-        mx = fold_max(mx, k8);
-        mn = fold_min(mn, k8);
+        mx = fold_max<T>(mx, k8);
+        mn = fold_min<T>(mn, k8);
         uint16_t* dst = kdst + (size_t)e * ks.entry + (size_t)pool_slot(ks, h, (uint32_t)e) * ks.head;
         *reinterpret_cast<ushort8*>(dst) = k8;
         *reinterpret_cast<ushort8*>(dst + kv_v_off) = v8;
     }
     *reinterpret_cast<ushort8*>(mmax) = mx;
     *reinterpret_cast<ushort8*>(mmin) = mn;
+}
+__global__ __launch_bounds__(256) void append_prefill_kernel(quest_paged_kv_t kv, quest_paged_kv_t meta,
+                                                             const uint16_t* __restrict__ key,
+                                                             const uint16_t* __restrict__ value,
+                                                             uint32_t append_len) {
+    append_prefill_body<half_t>(kv, meta, key, value, append_len);
+}
+__global__ __launch_bounds__(256) void append_prefill_kernel_bf16(quest_paged_kv_t kv, quest_paged_kv_t meta,
+                                                                  const uint16_t* __restrict__ key,
+                                                                  const uint16_t* __restrict__ value,
+                                                                  uint32_t append_len) {
+    append_prefill_body<bf16_t>(kv, meta, key, value, append_len);
 }
 
 __global__ void step_state_advance_kernel(quest_step_state_t* st, const int32_t* __restrict__ kv_table,
@@ -112,6 +138,7 @@ extern "C" uint32_t quest_pool_slot(uint32_t layout, uint32_t num_heads, uint32_
 }
 
 int check_pool(const quest_paged_kv_t& p) {
+    if (p.dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!p.data || !p.indices) return QUEST_EINVAL;
     if (p.layout > QUEST_LAYOUT_NHD_ROT) return QUEST_EINVAL;
     if (p.num_heads == 0 || p.page_size == 0) return QUEST_EINVAL;
@@ -127,12 +154,13 @@ using namespace quest;
 // one token per sequence into the pools; a state-driven launch (`state` != NULL) reads lengths / last pages per sequence
 static int append_decode(const void* k, const void* v, quest_paged_kv_t kv, quest_paged_kv_t metadata,
                          const quest_step_state_t* state, uint32_t n_seqs, quest_stream_t stream) {
+    if (int e = check_dtype_pair(kv, metadata)) return e;
     if (!k || !v || n_seqs == 0) return QUEST_EINVAL;
     if (int e = check_pool_pair(kv, metadata, state != nullptr, false)) return e;
     const uint32_t threads = kv.num_heads * (kv.head_dim / kVec);
     const uint32_t block = 256, grid = (threads + block - 1) / block;
-    hipLaunchKernelGGL(append_decode_kernel, dim3(grid, n_seqs), dim3(block), 0, (hipStream_t)stream, kv, metadata,
-                       (const uint16_t*)k, (const uint16_t*)v, state);
+    hipLaunchKernelGGL((kv.dtype == QUEST_DTYPE_BF16 ? append_decode_kernel_bf16 : append_decode_kernel), dim3(grid, n_seqs),
+                       dim3(block), 0, (hipStream_t)stream, kv, metadata, (const uint16_t*)k, (const uint16_t*)v, state);
     QUEST_LAUNCH_CHECK();
     return 0;
 }
@@ -159,6 +187,7 @@ extern "C" int quest_append_kv_cache_decode_batched(const void* k, const void* v
 extern "C" int quest_append_kv_cache_prefill(const void* k, const void* v, uint32_t append_len,
                                              uint32_t n_pages_host, quest_paged_kv_t kv,
                                              quest_paged_kv_t metadata, quest_stream_t stream) {
+    if (int e = check_dtype_pair(kv, metadata)) return e;
     if (!k || !v || append_len == 0 || n_pages_host == 0) return QUEST_EINVAL;
     if (!kv.indptr || !metadata.indptr) return QUEST_EINVAL;
     if (int e = check_pool_pair(kv, metadata, false, false)) return e;
@@ -171,8 +200,8 @@ extern "C" int quest_append_kv_cache_prefill(const void* k, const void* v, uint3
     const uint32_t rows_per_block = block / (kv.head_dim / kVec);
     const uint64_t rows = pages * kv.num_heads;
     const uint32_t grid = (uint32_t)((rows + rows_per_block - 1) / rows_per_block);
-    hipLaunchKernelGGL(append_prefill_kernel, dim3(grid), dim3(block), 0, (hipStream_t)stream, kv, metadata,
-                       (const uint16_t*)k, (const uint16_t*)v, append_len);
+    hipLaunchKernelGGL((kv.dtype == QUEST_DTYPE_BF16 ? append_prefill_kernel_bf16 : append_prefill_kernel), dim3(grid),
+                       dim3(block), 0, (hipStream_t)stream, kv, metadata, (const uint16_t*)k, (const uint16_t*)v, append_len);
     QUEST_LAUNCH_CHECK();
     return 0;
 }

@@ -5,17 +5,22 @@
 
 namespace quest {
 
-// fp16 max/min on bit patterns: NaN-suppressing, -0 < +0 -- the exact rule the oracle states
-// (oracle/quest_oracle.c qo_hmax/qo_hmin) so metadata is bit-identical.
+// max/min of 16-bit floats on bit patterns: NaN-suppressing, -0 < +0 -- the exact rule the oracle states
+// (oracle/quest_oracle.c qo_hmax/qo_hmin) so metadata is bit-identical.  The rule is the same for both element types;
+// what differs is where NaN starts: above the infinity pattern, 0x7c00 for fp16 and 0x7f80 for bf16.
+template <typename T>
+constexpr uint16_t kInfBits = kIsBf16<T> ? 0x7f80u : 0x7c00u;
+template <typename T>
 __device__ __forceinline__ uint16_t hmax_bits(uint16_t a, uint16_t b) {
-    const bool an = (a & 0x7fffu) > 0x7c00u, bn = (b & 0x7fffu) > 0x7c00u;
+    const bool an = (a & 0x7fffu) > kInfBits<T>, bn = (b & 0x7fffu) > kInfBits<T>;
     uint16_t r = half_key(a) >= half_key(b) ? a : b;
     if (an) r = bn ? (uint16_t)0x7fffu : b;
     else if (bn) r = a;
     return r;
 }
+template <typename T>
 __device__ __forceinline__ uint16_t hmin_bits(uint16_t a, uint16_t b) {
-    const bool an = (a & 0x7fffu) > 0x7c00u, bn = (b & 0x7fffu) > 0x7c00u;
+    const bool an = (a & 0x7fffu) > kInfBits<T>, bn = (b & 0x7fffu) > kInfBits<T>;
     uint16_t r = half_key(a) <= half_key(b) ? a : b;
     if (an) r = bn ? (uint16_t)0x7fffu : b;
     else if (bn) r = a;
@@ -24,21 +29,30 @@ __device__ __forceinline__ uint16_t hmin_bits(uint16_t a, uint16_t b) {
 
 typedef uint16_t ushort8 __attribute__((ext_vector_type(8)));
 
+template <typename T>
 __device__ __forceinline__ ushort8 fold_max(ushort8 m, ushort8 k) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) m[i] = hmax_bits(m[i], k[i]);
+    for (int i = 0; i < 8; ++i) m[i] = hmax_bits<T>(m[i], k[i]);
     return m;
 }
+template <typename T>
 __device__ __forceinline__ ushort8 fold_min(ushort8 m, ushort8 k) {
 #pragma unroll
-    for (int i = 0; i < 8; ++i) m[i] = hmin_bits(m[i], k[i]);
+    for (int i = 0; i < 8; ++i) m[i] = hmin_bits<T>(m[i], k[i]);
     return m;
 }
 
 constexpr uint16_t kHalfMax = 0x7bffu;     // +65504 (CUDART_MAX_NORMAL_FP16, decode_page.cuh:430-431)
 constexpr uint16_t kHalfNegMax = 0xfbffu;  // -65504
+// The values a new page's (max, min) entry starts from: the largest finite value of the element type, negative for the
+// max.  A bf16 pool takes bf16's own (+-3.39e38, 0x7f7f / 0xff7f), not +-65504: bf16 keys may lie beyond +-65504.
+template <typename T>
+constexpr uint16_t kElemMax = kIsBf16<T> ? (uint16_t)0x7f7fu : kHalfMax;
+template <typename T>
+constexpr uint16_t kElemNegMax = kIsBf16<T> ? (uint16_t)0xff7fu : kHalfNegMax;
 
 // Body of the decode append for global thread id `tid` (one thread = 8 halves of one head).
+template <typename T>
 __device__ __forceinline__ void append_decode_body(const quest_paged_kv_t& kv, const quest_paged_kv_t& meta,
                                                    const uint16_t* __restrict__ key,
                                                    const uint16_t* __restrict__ value, uint32_t tid) {
@@ -71,11 +85,11 @@ __device__ __forceinline__ void append_decode_body(const quest_paged_kv_t& kv, c
         mx = *reinterpret_cast<const ushort8*>(mmax);
         mn = *reinterpret_cast<const ushort8*>(mmin);
     } else {  // the token opens a new page: start from the sentinels, not from stale pool bytes
-        mx = (ushort8)(kHalfNegMax);
-        mn = (ushort8)(kHalfMax);
+        mx = (ushort8)(kElemNegMax<T>);
+        mn = (ushort8)(kElemMax<T>);
     }
-    mx = fold_max(mx, k8);
-    mn = fold_min(mn, k8);
+    mx = fold_max<T>(mx, k8);
+    mn = fold_min<T>(mn, k8);
     *reinterpret_cast<ushort8*>(kdst) = k8;
     *reinterpret_cast<ushort8*>(kdst + pool_v_off(ks, kslot)) = v8;
     *reinterpret_cast<ushort8*>(mmax) = mx;

@@ -131,7 +131,7 @@ struct RowState {
 
 // Fold NG groups of R token rows (one load instruction each) into the row state with ONE rescale.
 // len[g] is the number of valid rows counted from group g's first row (<= 0: none).
-template <int D, int NG>
+template <typename T, int D, int NG>
 __device__ __forceinline__ void fold_groups(RowState<D>& st, const float8& qv, const half8 (&k)[NG], const half8 (&v)[NG],
                                             const int (&rows_left)[NG], int row) {
     constexpr int LPR = D / kVec;
@@ -139,7 +139,7 @@ __device__ __forceinline__ void fold_groups(RowState<D>& st, const float8& qv, c
     float m_new = st.m;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-        const float8 kf = to_f32(k[g]);
+        const float8 kf = to_f32<T>(k[g]);
         float dot = 0.f;
 #pragma unroll
         for (int i = 0; i < kVec; ++i) dot = __builtin_fmaf(qv[i], kf[i], dot);
@@ -156,7 +156,7 @@ __device__ __forceinline__ void fold_groups(RowState<D>& st, const float8& qv, c
         const bool valid = row < rows_left[g];
         const float p = valid ? __builtin_amdgcn_exp2f(s[g] - m_new) : 0.f;
         st.d += p;
-        const float8 vf = valid ? to_f32(v[g]) : (float8)(0.f);
+        const float8 vf = valid ? to_f32<T>(v[g]) : (float8)(0.f);
 #pragma unroll
         for (int i = 0; i < kVec; ++i) st.acc[i] = __builtin_fmaf(p, vf[i], st.acc[i]);
     }
@@ -174,7 +174,7 @@ constexpr uint32_t kMergeFastChunks = 32;  // = kMergePre * kMergeGroups <= kWav
 // barrier is the cross-group sum.  The association order is fixed (chunks g, g+4, g+8, ... ascending into partial sum
 // g; then ((s0 + s1) + s2) + s3), independent of NT.
 // s_red: kMergeGroups * D floats of LDS.
-template <int D, int NT>
+template <typename T, int D, int NT>
 __device__ __forceinline__ void merge_head_fast(const float* __restrict__ w, half_t* __restrict__ o_row, float* lse_ptr,
                                                 uint32_t n_chunks, uint32_t ws_stride, uint32_t tid, float* s_red) {
     constexpr int ITEMS = kMergeGroups * D, PASSES = (ITEMS + NT - 1) / NT;
@@ -214,7 +214,7 @@ __device__ __forceinline__ void merge_head_fast(const float* __restrict__ w, hal
         float tot = s_red[f];
 #pragma unroll
         for (int j = 1; j < kMergeGroups; ++j) tot += s_red[j * D + f];
-        o_row[f] = (half_t)(tot / dn);
+        o_row[f] = from_f32<T>(tot / dn);
         if (lse_ptr && f == 0) *lse_ptr = (Mw + __builtin_amdgcn_logf(dn)) * 0.6931471805599453f;
     }
 }
@@ -259,7 +259,7 @@ struct AppendRow {
     bool writer;
 };
 struct NoAppend {};
-template <int D, int S_T, int NW, bool APPEND = false, typename PageOf, typename App = NoAppend>
+template <typename T, int D, int S_T, int NW, bool APPEND = false, typename PageOf, typename App = NoAppend>
 __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView sv, const half8 q_raw, const uint32_t chunk,
                                              const uint32_t hq, const uint32_t slot_begin, const uint32_t slot_end,
                                              const uint32_t n_listed, const int wave, const int lane,
@@ -272,7 +272,7 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
     // term is split between the two so that the row-rotated pool (st.rot, quest_common.cuh walk_*) walks like the plain ones
     const uint32_t lane_off = walk_lane_off(p.st, hk, R, row, col * kVec);  // per lane, loop invariant
     const uint32_t v_off = pool_v_off(p.st, hk);                              // uniform
-    float8 qv = to_f32(q_raw);
+    float8 qv = to_f32<T>(q_raw);
     qv *= p.scale_log2;
     [[maybe_unused]] half8 app_kn, app_vn;
     [[maybe_unused]] const uint32_t app_e = p.last_page_len - 1u;  // row of the new token in the current page
@@ -288,10 +288,10 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
     };
 
     if constexpr (S_T > 0) {
-        constexpr int T = (S_T + R - 1) / R;  // load instructions per page per tensor
-        uint32_t uni[T];                        // uniform, loop invariant
+        constexpr int T_ = (S_T + R - 1) / R;  // load instructions per page per tensor
+        uint32_t uni[T_];                        // uniform, loop invariant
 #pragma unroll
-        for (int t = 0; t < T; ++t) uni[t] = walk_uniform(p.st, hk, R, t);
+        for (int t = 0; t < T_; ++t) uni[t] = walk_uniform(p.st, hk, R, t);
         for (uint32_t s0 = slot_begin + wave; s0 < slot_end; s0 += 2 * NW) {
             const uint32_t s1 = s0 + NW;
             const bool has1 = s1 < slot_end;
@@ -301,12 +301,12 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
             const int len1 = has1 ? (s1 < n_listed ? S_T : (int)p.last_page_len) : 0;
             const half_t* b0 = p.kv + (size_t)pg0 * p.st.page;
             const half_t* b1 = p.kv + (size_t)pg1 * p.st.page;
-            half8 k[2 * T], v[2 * T];
-            int left[2 * T];
+            half8 k[2 * T_], v[2 * T_];
+            int left[2 * T_];
 #pragma unroll
-            for (int t = 0; t < T; ++t) {
+            for (int t = 0; t < T_; ++t) {
                 left[t] = len0 - t * R;
-                left[T + t] = len1 - t * R;
+                left[T_ + t] = len1 - t * R;
                 // rows past the page's length exist in the pool (the page is allocated) but hold
                 // stale bytes; they are fetched only for the sequence's last page and masked in fold
                 k[t] = ld8_kv(b0 + uni[t] + lane_off);
@@ -314,24 +314,24 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
             }
             if (has1) {  // wave-uniform (a likely-taken hint here cost 3.5 us per batched launch: measured, r3j)
 #pragma unroll
-                for (int t = 0; t < T; ++t) {
-                    k[T + t] = ld8_kv(b1 + uni[t] + lane_off);
-                    v[T + t] = ld8_kv(b1 + uni[t] + lane_off + v_off);
+                for (int t = 0; t < T_; ++t) {
+                    k[T_ + t] = ld8_kv(b1 + uni[t] + lane_off);
+                    v[T_ + t] = ld8_kv(b1 + uni[t] + lane_off + v_off);
                 }
                 if constexpr (APPEND) {
                     if (s0 >= n_listed || s1 >= n_listed) {  // wave-uniform: one of the two is the current page
-                        const int at = s0 >= n_listed ? 0 : T;
+                        const int at = s0 >= n_listed ? 0 : T_;
 #pragma unroll
-                        for (int t = 0; t < 2 * T; ++t)
-                            if (t >= at && t < at + T && (uint32_t)((t - at) * R + row) == app_e) k[t] = app_kn, v[t] = app_vn;
+                        for (int t = 0; t < 2 * T_; ++t)
+                            if (t >= at && t < at + T_ && (uint32_t)((t - at) * R + row) == app_e) k[t] = app_kn, v[t] = app_vn;
                     }
                 }
-                fold_groups<D, 2 * T>(st, qv, k, v, left, row);
+                fold_groups<T, D, 2 * T_>(st, qv, k, v, left, row);
             } else {
-                half8 k0[T], v0[T];
-                int left0[T];
+                half8 k0[T_], v0[T_];
+                int left0[T_];
 #pragma unroll
-                for (int t = 0; t < T; ++t) {
+                for (int t = 0; t < T_; ++t) {
                     k0[t] = k[t];
                     v0[t] = v[t];
                     left0[t] = left[t];
@@ -339,11 +339,11 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
                 if constexpr (APPEND) {
                     if (s0 >= n_listed) {
 #pragma unroll
-                        for (int t = 0; t < T; ++t)
+                        for (int t = 0; t < T_; ++t)
                             if ((uint32_t)(t * R + row) == app_e) k0[t] = app_kn, v0[t] = app_vn;
                     }
                 }
-                fold_groups<D, T>(st, qv, k0, v0, left0, row);
+                fold_groups<T, D, T_>(st, qv, k0, v0, left0, row);
             }
         }
     } else {
@@ -362,7 +362,7 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
                 const half_t* ptr = b + (size_t)e * p.st.entry + (size_t)pool_slot(p.st, hk, e) * p.st.head + col * kVec;
                 k1[0] = ld8(ptr);
                 v1[0] = ld8(ptr + v_off);
-                fold_groups<D, 1>(st, qv, k1, v1, left, row);
+                fold_groups<T, D, 1>(st, qv, k1, v1, left, row);
             }
         }
     }
@@ -376,10 +376,10 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
             st8(dst + v_off, app_vn);
             const ushort8 k8 = __builtin_bit_cast(ushort8, app_kn);
             // a token that opens a page starts from the sentinels, not from stale pool bytes
-            const ushort8 mx0 = app_e > 0 ? app.mx : (ushort8)(kHalfNegMax), mn0 = app_e > 0 ? app.mn : (ushort8)(kHalfMax);
+            const ushort8 mx0 = app_e > 0 ? app.mx : (ushort8)(kElemNegMax<T>), mn0 = app_e > 0 ? app.mn : (ushort8)(kElemMax<T>);
             uint16_t* me = reinterpret_cast<uint16_t*>(app.meta_entry) + col * kVec;
-            *reinterpret_cast<ushort8*>(me) = fold_max(mx0, k8);
-            *reinterpret_cast<ushort8*>(me + app.meta_v_off) = fold_min(mn0, k8);
+            *reinterpret_cast<ushort8*>(me) = fold_max<T>(mx0, k8);
+            *reinterpret_cast<ushort8*>(me + app.meta_v_off) = fold_min<T>(mn0, k8);
         }
     }
     QUEST_STAMP(6);
@@ -423,7 +423,7 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
             den += e * s_md[w][1];
         }
         if (p.n_chunks == 1) {
-            sv.o[(size_t)hq * D + f] = (half_t)(acc / den);
+            sv.o[(size_t)hq * D + f] = from_f32<T>(acc / den);
             if (QUEST_LSE_ENABLED && p.lse && f == 0) sv.lse[hq] = (M + __builtin_amdgcn_logf(den)) * 0.6931471805599453f;
             // (a wall-stamp build allocates the workspace for one-chunk plans too)
             if (f == 0) QUEST_WS_RECORD(sv.ws ? sv.ws + (size_t)hq * p.ws_stride : nullptr, D, p.ws_stride, slot_end > slot_begin ? slot_end - slot_begin : 0u);
@@ -455,7 +455,7 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
 // (chunk, hq, seq) are the workgroup's coordinates.
 // VF >= 0: the front-end variant (DecodeParams.vec_front) is a compile-time constant and the other variants' code is
 // not part of the kernel (the generic fused kernel carries all four: 27 KiB of code against 11 for one).
-template <int D, int S_T, int FC, int NW, int VF = -1>
+template <typename T, int D, int S_T, int FC, int NW, int VF = -1>
 __device__ __forceinline__ void sparse_decode_body(DecodeParams p, const uint32_t chunk, const uint32_t hq, const uint32_t seq,
                                                    const uint32_t num_qo_heads) {
     constexpr int LPR = D / kVec;
@@ -679,7 +679,7 @@ __device__ __forceinline__ void sparse_decode_body(DecodeParams p, const uint32_
         }  // n > 0
     }
     const int32_t* idx_row = sv.indices + (size_t)hq * p.idx_stride;  // uniform
-    attend_slots<D, S_T, NW>(attend_args(p), sv, q_raw, chunk, hq, slot_begin, slot_end, p.n_sel, wave, lane, [&](uint32_t slot) -> int32_t {
+    attend_slots<T, D, S_T, NW>(attend_args(p), sv, q_raw, chunk, hq, slot_begin, slot_end, p.n_sel, wave, lane, [&](uint32_t slot) -> int32_t {
         if constexpr (FC > 0) return s_sel[slot - slot_begin];
         else return idx_row[slot];
     } QUEST_TL_ARG QUEST_WS_ARG);
@@ -705,7 +705,7 @@ __device__ __forceinline__ void sparse_decode_body(DecodeParams p, const uint32_
 // capacity only; a tile key beyond the sequence's n_tiles (never written by its estimate) is masked in pass 1, a column beyond n
 // in pass 2.  A sequence with an empty row (one page) or a budget of one page skips both passes and attends its current page.
 constexpr int kTileCols = 8;
-template <int D, int NW>
+template <typename T, int D, int NW>
 __device__ __forceinline__ void sparse_decode_tiles_body(DecodeParams p, const uint32_t chunk, const uint32_t hq,
                                                          const uint32_t seq, const uint32_t num_qo_heads) {
     constexpr int LPR = D / kVec, NT = NW * kWave, TM = 4, KC = 4;
@@ -805,7 +805,7 @@ __device__ __forceinline__ void sparse_decode_tiles_body(DecodeParams p, const u
     }
     __syncthreads();
     QUEST_STAMP(5);
-    attend_slots<D, 16, NW>(attend_args(p), sv, q_raw, chunk, hq, slot_begin, slot_end, p.n_sel, wave, lane,
+    attend_slots<T, D, 16, NW>(attend_args(p), sv, q_raw, chunk, hq, slot_begin, slot_end, p.n_sel, wave, lane,
                             [&](uint32_t slot) -> int32_t { return s_sel[slot - slot_begin]; } QUEST_TL_ARG QUEST_WS_ARG);
     QUEST_TL_REPORT(p, chunk, hq, seq, num_qo_heads);
 }

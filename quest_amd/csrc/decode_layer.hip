@@ -147,7 +147,7 @@ __global__ __launch_bounds__(kGvWaves* kWave, kGvWaves / 2) void gemv_kernel(Gem
     if (p.gamma) {
         float ss = 0.f;
         for (uint32_t v = tid; v < n_vec; v += kGvWaves * kWave) {
-            const float8 xf = to_f32(ld8(p.x + (size_t)v * kVec));
+            const float8 xf = to_f32<half_t>(ld8(p.x + (size_t)v * kVec));
 #pragma unroll
             for (int i = 0; i < kVec; ++i) ss = __builtin_fmaf(xf[i], xf[i], ss);
         }
@@ -161,7 +161,7 @@ __global__ __launch_bounds__(kGvWaves* kWave, kGvWaves / 2) void gemv_kernel(Gem
         for (uint32_t v = tid; v < pad_vec; v += kGvWaves * kWave) {
             half8 o = (half8)(half_t)0;
             if (v < n_vec) {
-                const float8 xf = to_f32(ld8(p.x + (size_t)v * kVec)), g = to_f32(ld8(p.gamma + (size_t)v * kVec));
+                const float8 xf = to_f32<half_t>(ld8(p.x + (size_t)v * kVec)), g = to_f32<half_t>(ld8(p.gamma + (size_t)v * kVec));
                 float8 rr;
 #pragma unroll
                 for (int i = 0; i < kVec; ++i) rr[i] = xf[i] * inv * g[i];
@@ -387,7 +387,7 @@ __global__ __launch_bounds__(NW* kWave, 2) void skinny_kernel(SkinnyArgs a) {  /
         for (uint32_t t = 0; t < a.n_tokens; ++t) {
             float ss = 0.f;
             for (uint32_t v = tid; v < n_vec; v += NW * kWave) {
-                const float8 xf = to_f32(ld8(p.x + (size_t)t * a.x_stride + (size_t)v * kVec));
+                const float8 xf = to_f32<half_t>(ld8(p.x + (size_t)t * a.x_stride + (size_t)v * kVec));
 #pragma unroll
                 for (int i = 0; i < kVec; ++i) ss = __builtin_fmaf(xf[i], xf[i], ss);
             }
@@ -416,12 +416,12 @@ __global__ __launch_bounds__(NW* kWave, 2) void skinny_kernel(SkinnyArgs a) {  /
         const uint32_t k0 = (wave + NW * s) * 128u + blk * 8u;
         const bool in = k0 < p.in_dim;
         float8 gf;
-        if (norm) gf = to_f32(ld8(gamma_s + (in ? k0 : 0u)));
+        if (norm) gf = to_f32<half_t>(ld8(gamma_s + (in ? k0 : 0u)));
 #pragma unroll
         for (int t = 0; t < TG; ++t) {
             half8 b = xv[u][t];
             if (norm) {
-                const float8 xf = to_f32(b);
+                const float8 xf = to_f32<half_t>(b);
                 float8 rr;
 #pragma unroll
                 for (int i = 0; i < kVec; ++i) rr[i] = xf[i] * inv[t] * gf[i];
@@ -636,7 +636,7 @@ __global__ __launch_bounds__(kPsWaves* kWave, 4) void persist_kernel(SkinnyArgs 
             half8 o = xr[i];
             const bool in = e < x_tot && v * kVec < p.in_dim;
             if (norm && in) {
-                const float8 xf = to_f32(o), g = to_f32(ld8(p.gamma + v * kVec));
+                const float8 xf = to_f32<half_t>(o), g = to_f32<half_t>(ld8(p.gamma + v * kVec));
                 const float inv = s_inv[t];
                 float8 rr;
 #pragma unroll
@@ -670,7 +670,7 @@ __global__ __launch_bounds__(kPsWaves* kWave, 4) void persist_kernel(SkinnyArgs 
             const uint32_t e = tid + (uint32_t)i * kPsWaves * kWave, t = __umulhi(e, pl.vpp_magic);
             float ss = 0.f;
             if (e < x_tot && (e - t * vpp) * kVec < p.in_dim) {
-                const float8 xf = to_f32(xr[i]);
+                const float8 xf = to_f32<half_t>(xr[i]);
 #pragma unroll
                 for (int c = 0; c < kVec; ++c) ss = __builtin_fmaf(xf[c], xf[c], ss);
             }

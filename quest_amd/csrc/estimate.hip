@@ -27,11 +27,14 @@ namespace quest {
 // The leading scalar arguments are the fields the first loads of a workgroup need (role, page-table entry, metadata
 // rows, live length): scalar kernel arguments are preloaded into SGPRs at wave launch (14 dwords beside the kernarg
 // pointer, build.py), a struct passed by value is not -- its remaining fields arrive by s_load while those loads fly.
-template <int D, int G, bool HND, int EWV>
-__global__ __launch_bounds__(EWV* kWave, QUEST_EST_MIN_WAVES) void estimate_kernel(
-    const half_t* __restrict__ q, void* a_meta_data, const int32_t* a_meta_indices, const quest_step_state_t* a_state,
-    uint32_t n_out, uint32_t a_num_heads, uint32_t a_page_size, uint32_t a_tile_log2, uint32_t a_append_from,
-    uint32_t a_meta_table_stride, half_t* __restrict__ o, quest_paged_kv_t meta, AppendTail tail) {
+#define QUEST_ESTIMATE_PARAMS                                                                                            \
+    const half_t *__restrict__ q, void *a_meta_data, const int32_t *a_meta_indices, const quest_step_state_t *a_state,   \
+        uint32_t n_out, uint32_t a_num_heads, uint32_t a_page_size, uint32_t a_tile_log2, uint32_t a_append_from,        \
+        uint32_t a_meta_table_stride, half_t *__restrict__ o, quest_paged_kv_t meta, AppendTail tail
+#define QUEST_ESTIMATE_ARGS \
+    q, a_meta_data, a_meta_indices, a_state, n_out, a_num_heads, a_page_size, a_tile_log2, a_append_from, a_meta_table_stride, o, meta, tail
+template <typename T, int D, int G, bool HND, int EWV>
+__device__ __forceinline__ void estimate_kernel_body(QUEST_ESTIMATE_PARAMS) {
     // a_append_from: first append block (= est_blocks), 0xffffffff when no append rides in this launch
     meta.data = a_meta_data, meta.indices = a_meta_indices, meta.num_heads = a_num_heads, meta.page_size = a_page_size;
     // a_tile_log2: log2(tile heads) | row-rotated pool << 8 (the layout decides the first loads' addresses, so it travels in
@@ -59,14 +62,23 @@ __global__ __launch_bounds__(EWV* kWave, QUEST_EST_MIN_WAVES) void estimate_kern
         }
         // The appended token only touches the CURRENT page's KV entry and metadata entry (index n_out),
         // which the estimate excludes (e < n_out), so the two halves of the launch share no byte.
-        append_decode_body(tail.kv, meta, tail.key, tail.value, (blockIdx.x - tail.est_blocks) * (EWV * kWave) + threadIdx.x);
+        append_decode_body<T>(tail.kv, meta, tail.key, tail.value, (blockIdx.x - tail.est_blocks) * (EWV * kWave) + threadIdx.x);
         return;
     }
     extern __shared__ __attribute__((aligned(16))) unsigned char est_smem[];
     __shared__ uint32_t s_literal[EWV];
     const uint32_t head_tiles = meta.num_heads >> tail.tile_log2;
-    estimate_tile<D, G, HND, EWV, 1>(q, o, meta, n_out, tail, blockIdx.x / head_tiles, blockIdx.x % head_tiles,
-                                     threadIdx.x, est_smem, s_literal, seq * meta.num_heads * G);
+    estimate_tile<T, D, G, HND, EWV, 1>(q, o, meta, n_out, tail, blockIdx.x / head_tiles, blockIdx.x % head_tiles,
+                                        threadIdx.x, est_smem, s_literal, seq * meta.num_heads * G);
+}
+// fp16 pools and bf16 pools (quest_paged_kv_t.dtype): separately named kernels over the one body
+template <int D, int G, bool HND, int EWV>
+__global__ __launch_bounds__(EWV* kWave, QUEST_EST_MIN_WAVES) void estimate_kernel(QUEST_ESTIMATE_PARAMS) {
+    estimate_kernel_body<half_t, D, G, HND, EWV>(QUEST_ESTIMATE_ARGS);
+}
+template <int D, int G, bool HND, int EWV>
+__global__ __launch_bounds__(EWV* kWave, QUEST_EST_MIN_WAVES) void estimate_kernel_bf16(QUEST_ESTIMATE_PARAMS) {
+    estimate_kernel_body<bf16_t, D, G, HND, EWV>(QUEST_ESTIMATE_ARGS);
 }
 
 // Tile shape of a launch with EWV-wave workgroups: kv heads per tile (`hw`) and whether the shape can be served.
@@ -100,14 +112,15 @@ static int launch_estimate_w(const void* q, void* o, uint32_t n_out, const quest
     if (tail.enabled) blocks += (meta.num_heads * (D / kVec) + EWV * kWave - 1) / (EWV * kWave);
     if (blocks == 0) return 0;
     dim3 grid(blocks, n_seqs);
-    const size_t lds = est_tile_lds_bytes(hw, G, D, ew);
+    const bool bf = meta.dtype == QUEST_DTYPE_BF16;
+    const size_t lds = est_tile_lds_bytes(hw, G, D, ew, bf);
     const uint32_t append_from = tail.enabled ? tail.est_blocks : 0xffffffffu;
     if (hnd)
-        hipLaunchKernelGGL((estimate_kernel<D, G, true, EWV>), grid, dim3(EWV * kWave), lds, s, (const half_t*)q, meta.data,
+        hipLaunchKernelGGL((bf ? estimate_kernel_bf16<D, G, true, EWV> : estimate_kernel<D, G, true, EWV>), grid, dim3(EWV * kWave), lds, s, (const half_t*)q, meta.data,
                            meta.indices, tail.state, n_out, meta.num_heads, meta.page_size, tail.tile_log2, append_from,
                            tail.meta_table_stride, (half_t*)o, meta, tail);
     else
-        hipLaunchKernelGGL((estimate_kernel<D, G, false, EWV>), grid, dim3(EWV * kWave), lds, s, (const half_t*)q, meta.data,
+        hipLaunchKernelGGL((bf ? estimate_kernel_bf16<D, G, false, EWV> : estimate_kernel<D, G, false, EWV>), grid, dim3(EWV * kWave), lds, s, (const half_t*)q, meta.data,
                            meta.indices, tail.state, n_out, meta.num_heads, meta.page_size,
                            tail.tile_log2 | (meta.layout == QUEST_LAYOUT_NHD_ROT ? 1u << 8 : 0u), append_from,
                            tail.meta_table_stride, (half_t*)o, meta, tail);
@@ -150,6 +163,8 @@ using namespace quest;
 
 static int estimate_entry(const void* q, void* o, uint32_t num_qo_heads, uint32_t n_out, const quest_paged_kv_t& metadata,
                           const AppendTail& tail, hipStream_t s, uint32_t n_seqs) {
+    // element type: the metadata view's, and the KV view's of a launch that also appends must agree with it
+    if (int e = tail.enabled ? check_dtype_pair(tail.kv, metadata) : check_dtype(metadata)) return e;
     if (!q || !metadata.data || !metadata.indices) return QUEST_EINVAL;
     if (metadata.layout > QUEST_LAYOUT_NHD_ROT || metadata.num_heads == 0 || metadata.page_size == 0) return QUEST_EINVAL;
     if (num_qo_heads == 0 || num_qo_heads % metadata.num_heads != 0) return QUEST_EINVAL;
@@ -182,6 +197,7 @@ static int append_estimate_state(const void* k, const void* v, quest_paged_kv_t 
                                  uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
                                  quest_paged_kv_t metadata, const quest_step_state_t* state, quest_batch_t batch,
                                  quest_stream_t stream, uint32_t tile_off) {
+    if (int e = check_dtype_pair(kv, metadata)) return e;
     if (!k || !v || !state || max_n_out == 0 || o_stride < max_n_out || batch.n_seqs == 0) return QUEST_EINVAL;
     if (tile_off && (tile_off % 8u != 0 || tile_off < ((max_n_out + 7u) & ~7u) ||
                      o_stride < tile_off + ((((max_n_out + 7u) / 8u) + 3u) & ~3u)))
@@ -197,6 +213,7 @@ static int append_estimate_state(const void* k, const void* v, quest_paged_kv_t 
 extern "C" int quest_estimate_attn_score_batched(const void* q, void* o, uint32_t num_qo_heads, uint32_t o_stride,
                                                  uint32_t max_n_out, quest_paged_kv_t metadata,
                                                  const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream) {
+    if (int e = check_dtype(metadata)) return e;
     if (!state || max_n_out == 0 || o_stride < max_n_out || batch.n_seqs == 0) return QUEST_EINVAL;
     if (batch.n_seqs > 1 && (uint64_t)batch.meta_table_stride * metadata.page_size < max_n_out) return QUEST_EINVAL;
     metadata.last_page_len = 1;  // placeholder; the kernel reads the live length from `state`
@@ -255,6 +272,7 @@ extern "C" int quest_append_estimate_tiles_batched(const void* k, const void* v,
 extern "C" int quest_append_estimate_strided(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
                                              uint32_t num_qo_heads, uint32_t n_out, uint32_t o_stride,
                                              quest_paged_kv_t metadata, quest_stream_t stream) {
+    if (int e = check_dtype_pair(kv, metadata)) return e;
     if (!k || !v || (o_stride != 0 && o_stride < n_out)) return QUEST_EINVAL;
     if (int e = check_pool_pair(kv, metadata, false, false)) return e;
     AppendTail tail = append_tail(k, v, kv, o_stride);

@@ -59,7 +59,20 @@ struct AppendTail {  // optional decode-append riding in the same launch (blocks
 // tile is (entry tile `et`, head tile `ht`).  With TPB > 1 the tiles of a workgroup share its barriers, so a tile
 // that lies past the live length runs through with clamped loads and masked stores instead of returning.
 // `smem` = the tile's dynamic LDS (est_tile_lds_bytes), `s_literal` = EWV words of LDS.
-template <int D, int G, bool HND, int EWV, int TPB>
+//
+// Element type T = bf16_t: the literal form ALWAYS.  The fast form above stands on three fp16 facts that bf16 lacks on
+// gfx950: packed max / min of two elements per instruction (there is no v_pk_max/min for bf16), v_fma_mix_f32 (reads its
+// operands as fp16 only), and a product that is exact in fp32 (bf16 x bf16 has 16 significant bits but its exponent
+// leaves fp32's range, so `fma(q, x, acc)` and `acc + q * x` part ways once q * x overflows or goes subnormal).  A fast
+// form rebuilt from fp32 instructions (shift / mask to fp32, v_max_f32 + v_min_f32 shared by the group, then select,
+// multiply, add per query head) was NOT built: counted from the instruction set -- a count, not a measurement -- it would
+// cost 4 + 3 G VALU operations per feature against the literal form's 2 + 4 G, i.e. more at MHA, the same at G = 2 and 16
+// against 18 at G = 4, where the literal form MEASURES slower than the fp16 kernel (by how much: DESIGN.md section 2,
+// profiles/bf16_vs_fp16_kernels.txt): a bf16 fast form for G >= 4 is open work.  So the bf16 kernel computes
+// bf16_rne(sum_d max(q * Kmax, q * Kmin)) as written, in the fp16 kernel's lane and tree order (8 features left to right
+// per lane, then the same row reduction), for any pool contents and any query.  Nothing is staged for a fast form: the
+// bf16 tile has no sign masks in LDS (est_tile_lds_bytes: q + score transpose only).
+template <typename T, int D, int G, bool HND, int EWV, int TPB>
 __device__ __forceinline__ void estimate_tile(const half_t* __restrict__ q, half_t* __restrict__ o, const quest_paged_kv_t& meta,
                                               uint32_t n_out, const AppendTail& tail, uint32_t et, uint32_t ht, uint32_t tid,
                                               unsigned char* est_smem, uint32_t* s_literal, uint32_t o_row0 = 0) {
@@ -76,8 +89,8 @@ __device__ __forceinline__ void estimate_tile(const half_t* __restrict__ q, half
     const uint32_t hw_l2 = tail.tile_log2, ew_l2 = (uint32_t)__builtin_ctz(ROWS) - hw_l2;
     const uint32_t HW = 1u << hw_l2, EW = 1u << ew_l2;
     half_t* q_s = reinterpret_cast<half_t*>(est_smem);                              // [HW*G][D]  q
-    uint16_t* neg_s = reinterpret_cast<uint16_t*>(q_s + (size_t)HW * G * D);        // [HW*G][D]  q < 0 ? 0xffff : 0
-    half_t* out_s = reinterpret_cast<half_t*>(neg_s + (size_t)HW * G * D);          // [HW*G][EW] scores
+    uint16_t* neg_s = reinterpret_cast<uint16_t*>(q_s + (size_t)HW * G * D);        // [HW*G][D]  q < 0 ? 0xffff : 0  (fp16 only)
+    half_t* out_s = reinterpret_cast<half_t*>(neg_s + (kIsBf16<T> ? (size_t)0 : (size_t)HW * G * D));  // [HW*G][EW] scores
     // s_literal[w]: some q element staged by wave w is zero or non-finite
 
     const int wave = tid >> 6, lane = tid & 63;
@@ -153,29 +166,35 @@ __device__ __forceinline__ void estimate_tile(const half_t* __restrict__ q, half
         if (vi < q_vecs) {
             const uint4 w = __builtin_bit_cast(uint4, qreg[t]);
             const uint32_t ww[4] = {w.x, w.y, w.z, w.w};
+            if constexpr (kIsBf16<T>) {  // literal form always: no sign masks, no test of q
+                st8(q_s + (size_t)vi * kVec, qreg[t]);
+                continue;
+            }
             uint32_t m[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 m[i] = ((ww[i] >> 15) & 0x00010001u) * 0xffffu;
-                // (|x| bits) - 1 >= 0x7bff  <=>  x is +-0, +-inf or NaN
+                // (|x| bits) - 1 >= 0x7bff  <=>  x is +-0, +-inf or NaN (fp16 encoding)
                 odd_q |= ((ww[i] & 0x7fffu) - 1u >= 0x7bffu) | (((ww[i] >> 16) & 0x7fffu) - 1u >= 0x7bffu);
             }
             st8(q_s + (size_t)vi * kVec, qreg[t]);
             *reinterpret_cast<uint4*>(neg_s + (size_t)vi * kVec) = make_uint4(m[0], m[1], m[2], m[3]);
         }
     }
-    {
+    if constexpr (!kIsBf16<T>) {
         const unsigned long long any = __ballot(odd_q);
         if (lane == 0) s_literal[wave] = any != 0ull;
     }
     __syncthreads();
-    uint32_t literal = 0;
+    uint32_t literal = kIsBf16<T> ? 1u : 0u;
+    if constexpr (!kIsBf16<T>) {
 #pragma unroll
-    for (int w = 0; w < EWV; ++w) literal |= s_literal[w];
-    literal = __builtin_amdgcn_readfirstlane(literal);
+        for (int w = 0; w < EWV; ++w) literal |= s_literal[w];
+        literal = __builtin_amdgcn_readfirstlane(literal);
+    }
 
     // (3) scores
-    if (QUEST_LIKELY(!literal)) {
+    if (!kIsBf16<T> && QUEST_LIKELY(!literal)) {
 #pragma unroll
         for (int j = 0; j < kEstIter; ++j) {
             const half8 hi = __builtin_elementwise_max(mx[j], mn[j]), lo = __builtin_elementwise_min(mx[j], mn[j]);
@@ -184,14 +203,14 @@ __device__ __forceinline__ void estimate_tile(const half_t* __restrict__ q, half
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 const uint32_t qh = hl[j] * G + g;  // query head inside the tile
-                const float8 qf = to_f32(ld8(q_s + (size_t)qh * D + col * kVec));
+                const float8 qf = to_f32<half_t>(ld8(q_s + (size_t)qh * D + col * kVec));
                 const uint4 nm = *reinterpret_cast<const uint4*>(neg_s + (size_t)qh * D + col * kVec);
                 uint4 sb;  // per 16-bit feature: q < 0 ? lo : hi
                 sb.x = (lb.x & nm.x) | (hb.x & ~nm.x);
                 sb.y = (lb.y & nm.y) | (hb.y & ~nm.y);
                 sb.z = (lb.z & nm.z) | (hb.z & ~nm.z);
                 sb.w = (lb.w & nm.w) | (hb.w & ~nm.w);
-                const float8 x = to_f32(__builtin_bit_cast(half8, sb));
+                const float8 x = to_f32<half_t>(__builtin_bit_cast(half8, sb));
                 float acc = 0.f;
 #pragma unroll
                 for (int i = 0; i < kVec; ++i) acc = __builtin_fmaf(qf[i], x[i], acc);
@@ -213,16 +232,16 @@ __device__ __forceinline__ void estimate_tile(const half_t* __restrict__ q, half
     } else {  // literal form of decode_attn.cuh:152-156 (zero / non-finite query element in the tile)
 #pragma unroll
         for (int j = 0; j < kEstIter; ++j) {
-            const float8 a = to_f32(mx[j]), b = to_f32(mn[j]);
+            const float8 a = to_f32<T>(mx[j]), b = to_f32<T>(mn[j]);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
                 const uint32_t qh = hl[j] * G + g;
-                const float8 qf = to_f32(ld8(q_s + (size_t)qh * D + col * kVec));
+                const float8 qf = to_f32<T>(ld8(q_s + (size_t)qh * D + col * kVec));
                 float acc = 0.f;
 #pragma unroll
                 for (int i = 0; i < kVec; ++i) acc += __builtin_fmaxf(qf[i] * a[i], qf[i] * b[i]);
                 acc = row_allreduce_sum_fast<LPR>(acc);
-                if (col == 0) out_s[qh * EW + el[j]] = (half_t)acc;
+                if (col == 0) out_s[qh * EW + el[j]] = from_f32<T>(acc);
             }
         }
     }
@@ -260,9 +279,9 @@ static inline uint32_t pick_tile_heads(uint32_t num_heads, uint32_t G, uint32_t 
     return 1;
 }
 
-// dynamic LDS of one tile: q + sign masks + score transpose
-__host__ __device__ inline size_t est_tile_lds_bytes(uint32_t hw, uint32_t G, uint32_t D, uint32_t ew) {
-    return (size_t)hw * G * (2 * D + ew) * sizeof(half_t);
+// dynamic LDS of one tile: q + sign masks (fp16: the fast form's; a bf16 tile has none) + score transpose
+__host__ __device__ inline size_t est_tile_lds_bytes(uint32_t hw, uint32_t G, uint32_t D, uint32_t ew, bool bf16) {
+    return (size_t)hw * G * ((bf16 ? 1 : 2) * D + ew) * sizeof(half_t);
 }
 
 }  // namespace quest

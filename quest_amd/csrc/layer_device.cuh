@@ -73,11 +73,11 @@ __device__ __forceinline__ uint16_t page_score_bits(const half8 mx, const half8 
         sb.y = (lb.y & nm.y) | (hb.y & ~nm.y);
         sb.z = (lb.z & nm.z) | (hb.z & ~nm.z);
         sb.w = (lb.w & nm.w) | (hb.w & ~nm.w);
-        const float8 x = to_f32(__builtin_bit_cast(half8, sb));
+        const float8 x = to_f32<half_t>(__builtin_bit_cast(half8, sb));
 #pragma unroll
         for (int i = 0; i < kVec; ++i) acc = __builtin_fmaf(qf[i], x[i], acc);
     } else {
-        const float8 a = to_f32(mx), b = to_f32(mn);
+        const float8 a = to_f32<half_t>(mx), b = to_f32<half_t>(mn);
 #pragma unroll
         for (int i = 0; i < kVec; ++i) acc += __builtin_fmaxf(qf[i] * a[i], qf[i] * b[i]);
     }
@@ -161,7 +161,7 @@ __device__ __forceinline__ void layer_decode_body(QUEST_LAYER_HEAD_PARAMS, const
     app.writer = hq % group == 0;
 
     // ---- estimate: wave w streams the metadata pages w, w + NW, ... (two per round), scores -> keys in LDS
-    const float8 qf = to_f32(q_raw);
+    const float8 qf = to_f32<half_t>(q_raw);
     uint4 nm;  // per 16-bit feature: q < 0 ? 0xffff : 0
     bool odd_q = false;  // a zero or non-finite query element (the monotone form needs finite non-zero q)
     {
@@ -322,7 +322,7 @@ __device__ __forceinline__ void layer_decode_body(QUEST_LAYER_HEAD_PARAMS, const
     sv.scores = nullptr;
     sv.ws = p.ws ? p.ws + seq_row * p.ws_stride : nullptr;
     sv.state = stp;
-    attend_slots<D, S_T, NW, true>(aa, sv, q_raw, 0u, hq, 0u, n_sel + 1u, n_sel, wave, lane,
+    attend_slots<half_t, D, S_T, NW, true>(aa, sv, q_raw, 0u, hq, 0u, n_sel + 1u, n_sel, wave, lane,
                                    [&](uint32_t slot) -> int32_t { return s_sel[slot]; } QUEST_TL_ARG QUEST_WS_ARG, app);
     if (tid == 0) QUEST_WS_RECORD_EXTRA(sv.ws ? sv.ws + (size_t)hq * p.ws_stride : nullptr, D, p.ws_stride, 5, ws_est);
 }

@@ -15,6 +15,17 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 typedef float float8 __attribute__((ext_vector_type(8)));
 
+// The second element type (QUEST_DTYPE_BF16).  The element type T of a kernel is a template parameter of the shared device
+// bodies, half_t or bf16_t.  Pools, queries, outputs and score rows are 16-bit storage whichever it is: pointers stay
+// half_t* and registers half8 / half4 (raw 16-byte / 8-byte pieces), addressing and loads do not depend on T.  What
+// depends on T is every place a VALUE is read or made: to_f32<T>, from_f32<T> (round to nearest even), the metadata
+// max / min and its sentinels (append_device.cuh), the estimate's fast form (estimate_device.cuh), the prefill's MFMA.
+typedef __bf16 bf16_t;
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+template <typename T>
+constexpr bool kIsBf16 = std::is_same<T, bf16_t>::value;
+
 constexpr int kWave = 64;
 constexpr int kVec = 8;  // halves per lane per 16-byte access
 
@@ -88,7 +99,24 @@ __device__ __forceinline__ half8 ld8_stream(const half_t* p) {
 }
 __device__ __forceinline__ void st8(half_t* p, half8 v) { *reinterpret_cast<half8*>(p) = v; }
 
-__device__ __forceinline__ float8 to_f32(half8 h) { return __builtin_convertvector(h, float8); }
+// 8 stored elements -> fp32 (exact for both types; bf16: a 16-bit shift per element).  No default for T here or below: a
+// call that forgets the element type does not compile (fp16-only code names half_t).
+template <typename T>
+__device__ __forceinline__ float8 to_f32(half8 h) {
+    if constexpr (kIsBf16<T>) return __builtin_convertvector(__builtin_bit_cast(bf16x8, h), float8);
+    else return __builtin_convertvector(h, float8);
+}
+// fp32 -> the stored form of T, round to nearest even (bf16: v_cvt_pk_bf16_f32)
+template <typename T>
+__device__ __forceinline__ half8 from_f32(float8 x) {
+    if constexpr (kIsBf16<T>) return __builtin_bit_cast(half8, __builtin_convertvector(x, bf16x8));
+    else return __builtin_convertvector(x, half8);
+}
+template <typename T>
+__device__ __forceinline__ half_t from_f32(float x) {
+    if constexpr (kIsBf16<T>) return __builtin_bit_cast(half_t, (bf16_t)x);
+    else return (half_t)x;
+}
 
 // Butterfly sum over the W lanes of a row, offsets W/2 .. 1, every lane ends with the same bits: the
 // reduction order of the reference kernels (decode_attn.cuh:101-104, :157-160).  Each step is a
@@ -253,7 +281,9 @@ __device__ __forceinline__ uint32_t wave_scan_incl_dpp(uint32_t x) {
 __device__ __forceinline__ uint16_t half_bits(half_t h) { return __builtin_bit_cast(uint16_t, h); }
 __device__ __forceinline__ half_t bits_half(uint16_t b) { return __builtin_bit_cast(half_t, b); }
 
-// Order-preserving 16-bit key of an fp16 bit pattern (RAFT radix-select twiddle).
+// Order-preserving 16-bit key of an fp16 bit pattern (RAFT radix-select twiddle).  The twiddle orders any 16-bit
+// sign-magnitude float, so it is bf16's key as well (same placement of -0 < +0, infinities and NaN patterns at the ends):
+// the top-k code (topk.hip, topk_select.cuh, topk_bitmap.cuh, the fused front ends) has no element type.
 __device__ __forceinline__ uint32_t half_key(uint16_t b) {
     return (b & 0x8000u) ? (uint32_t)(uint16_t)~b : (uint32_t)(b | 0x8000u);
 }

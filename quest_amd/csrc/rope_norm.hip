@@ -13,11 +13,12 @@
 
 namespace quest {
 
-template <int D>
-__global__ __launch_bounds__(256) void rope_kernel(half_t* __restrict__ q, half_t* __restrict__ k, uint32_t n,
-                                                   uint32_t past_len, uint32_t hq, uint32_t hk, float rcp_scale,
-                                                   float log2_rcp_theta, const float* __restrict__ inv_freq, float attn,
-                                                   const quest_step_state_t* state) {
+#define QUEST_ROPE_PARAMS                                                                                         \
+    half_t *__restrict__ q, half_t *__restrict__ k, uint32_t n, uint32_t past_len, uint32_t hq, uint32_t hk,      \
+        float rcp_scale, float log2_rcp_theta, const float *__restrict__ inv_freq, float attn, const quest_step_state_t *state
+// T: the element type of q and k (the arithmetic is fp32 either way; the result is rounded to T once, to nearest even)
+template <typename T, int D>
+__device__ __forceinline__ void rope_body(QUEST_ROPE_PARAMS) {
     // state-driven: row i is the decode token of sequence i (one row for a single sequence)
     // inv_freq (uniform): NULL = the formula, else the [D/2] frequency table with cos / sin scaled by attn
     constexpr int LPR = D / kVec;
@@ -29,7 +30,7 @@ __global__ __launch_bounds__(256) void rope_kernel(half_t* __restrict__ q, half_
     const uint32_t tok = vec / per_tok, h = vec % per_tok;
     half_t* x = (h < hq) ? q + ((size_t)tok * hq + h) * D : k + ((size_t)tok * hk + (h - hq)) * D;
     x += col * kVec;
-    const float8 self = to_f32(ld8(x));
+    const float8 self = to_f32<T>(ld8(x));
     const float pos = state ? (float)(state[tok].seq_len - 1) : (float)(past_len + tok);
     float8 out;
 #pragma unroll
@@ -44,18 +45,27 @@ __global__ __launch_bounds__(256) void rope_kernel(half_t* __restrict__ q, half_
         if (inv_freq) s *= attn, c *= attn;
         out[i] = self[i] * c + (d < D / 2 ? -other : other) * s;
     }
-    st8(x, __builtin_convertvector(out, half8));
+    st8(x, from_f32<T>(out));
+}
+template <int D>
+__global__ __launch_bounds__(256) void rope_kernel(QUEST_ROPE_PARAMS) {
+    rope_body<half_t, D>(q, k, n, past_len, hq, hk, rcp_scale, log2_rcp_theta, inv_freq, attn, state);
+}
+template <int D>
+__global__ __launch_bounds__(256) void rope_kernel_bf16(QUEST_ROPE_PARAMS) {
+    rope_body<bf16_t, D>(q, k, n, past_len, hq, hk, rcp_scale, log2_rcp_theta, inv_freq, attn, state);
 }
 
-__global__ __launch_bounds__(1024) void rms_norm_kernel(const half_t* __restrict__ in, const half_t* __restrict__ w,
-                                                        half_t* __restrict__ out, uint32_t cols, float eps) {
+template <typename T>
+__device__ __forceinline__ void rms_norm_body(const half_t* __restrict__ in, const half_t* __restrict__ w,
+                                              half_t* __restrict__ out, uint32_t cols, float eps) {
     __shared__ float s_part[16];
     __shared__ float s_inv;
     const size_t row = blockIdx.x;
     const half_t* x = in + row * cols;
     float ss = 0.f;
     for (uint32_t c = threadIdx.x * kVec; c < cols; c += blockDim.x * kVec) {
-        const float8 v = to_f32(ld8(x + c));
+        const float8 v = to_f32<T>(ld8(x + c));
 #pragma unroll
         for (int i = 0; i < kVec; ++i) ss = __builtin_fmaf(v[i], v[i], ss);
     }
@@ -71,12 +81,20 @@ __global__ __launch_bounds__(1024) void rms_norm_kernel(const half_t* __restrict
     __syncthreads();
     const float inv = s_inv;
     for (uint32_t c = threadIdx.x * kVec; c < cols; c += blockDim.x * kVec) {
-        const float8 v = to_f32(ld8(x + c)), g = to_f32(ld8(w + c));
+        const float8 v = to_f32<T>(ld8(x + c)), g = to_f32<T>(ld8(w + c));
         float8 r;
 #pragma unroll
         for (int i = 0; i < kVec; ++i) r[i] = v[i] * inv * g[i];
-        st8(out + row * cols + c, __builtin_convertvector(r, half8));
+        st8(out + row * cols + c, from_f32<T>(r));
     }
+}
+__global__ __launch_bounds__(1024) void rms_norm_kernel(const half_t* __restrict__ in, const half_t* __restrict__ w,
+                                                        half_t* __restrict__ out, uint32_t cols, float eps) {
+    rms_norm_body<half_t>(in, w, out, cols, eps);
+}
+__global__ __launch_bounds__(1024) void rms_norm_kernel_bf16(const half_t* __restrict__ in, const half_t* __restrict__ w,
+                                                             half_t* __restrict__ out, uint32_t cols, float eps) {
+    rms_norm_body<bf16_t>(in, w, out, cols, eps);
 }
 
 }  // namespace quest
@@ -85,15 +103,17 @@ using namespace quest;
 
 static int rope_launch(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads, uint32_t num_kv_heads,
                        uint32_t head_dim, float rcp_scale, float log2_rcp_theta, const float* inv_freq, float attn,
-                       const quest_step_state_t* state, quest_stream_t stream) {
+                       const quest_step_state_t* state, quest_stream_t stream, uint32_t dtype = QUEST_DTYPE_F16) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!q || !k || num_qo_heads == 0 || num_kv_heads == 0) return QUEST_EINVAL;
     if (n == 0) return 0;
+    const bool bf = dtype == QUEST_DTYPE_BF16;
     const uint32_t vecs = n * (num_qo_heads + num_kv_heads);
     hipStream_t s = (hipStream_t)stream;
 #define QUEST_ROPE_CASE(DD)                                                                                       \
     case DD: {                                                                                                    \
         const uint32_t rpb = 256 / (DD / kVec);                                                                   \
-        hipLaunchKernelGGL((rope_kernel<DD>), dim3((vecs + rpb - 1) / rpb), dim3(256), 0, s, (half_t*)q,          \
+        hipLaunchKernelGGL((bf ? rope_kernel_bf16<DD> : rope_kernel<DD>), dim3((vecs + rpb - 1) / rpb), dim3(256), 0, s, (half_t*)q,          \
                            (half_t*)k, n, past_kv_len, num_qo_heads, num_kv_heads, rcp_scale, log2_rcp_theta,    \
                            inv_freq, attn, state);                                                               \
         break;                                                                                                    \
@@ -147,15 +167,43 @@ extern "C" int quest_apply_rope_in_place_freqs(void* q, void* k, uint32_t n, uin
                        states, stream);
 }
 
-extern "C" int quest_rms_norm_forward(const void* input, const void* weight, void* output, uint32_t rows, uint32_t cols,
-                                      float epsilon, quest_stream_t stream) {
+// The two operators that come with neither a pool view nor a handler get ONE typed entry each (the element type as an
+// argument); the existing entries keep their signatures and mean fp16.
+extern "C" int quest_apply_rope_in_place_dtype(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
+                                               uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
+                                               const float* inv_freq, float attention_factor,
+                                               const quest_step_state_t* states, uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
+    if (inv_freq) {
+        if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
+        return rope_launch(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, 1.0f, 0.f, inv_freq, attention_factor,
+                           states, stream, dtype);
+    }
+    if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
+    return rope_launch(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, 1.0f / rope_scale, -log2f(rope_theta),
+                       nullptr, 1.0f, states, stream, dtype);
+}
+
+static int rms_norm(const void* input, const void* weight, void* output, uint32_t rows, uint32_t cols, float epsilon,
+                    uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!input || !weight || !output) return QUEST_EINVAL;
     if (cols == 0 || cols % 8 != 0) return QUEST_EUNSUPPORTED;  // rms_norm.cu:164-166
     if (rows == 0) return 0;
     uint32_t threads = (cols / 8 + 63) / 64 * 64;
     if (threads > 1024) threads = 1024;
-    hipLaunchKernelGGL(rms_norm_kernel, dim3(rows), dim3(threads), 0, (hipStream_t)stream, (const half_t*)input,
+    hipLaunchKernelGGL((dtype == QUEST_DTYPE_BF16 ? rms_norm_kernel_bf16 : rms_norm_kernel), dim3(rows), dim3(threads), 0, (hipStream_t)stream, (const half_t*)input,
                        (const half_t*)weight, (half_t*)output, cols, epsilon);
     QUEST_LAUNCH_CHECK();
     return 0;
+}
+
+extern "C" int quest_rms_norm_forward(const void* input, const void* weight, void* output, uint32_t rows, uint32_t cols,
+                                      float epsilon, quest_stream_t stream) {
+    return rms_norm(input, weight, output, rows, cols, epsilon, QUEST_DTYPE_F16, stream);
+}
+
+extern "C" int quest_rms_norm_forward_dtype(const void* input, const void* weight, void* output, uint32_t rows, uint32_t cols,
+                                            float epsilon, uint32_t dtype, quest_stream_t stream) {
+    return rms_norm(input, weight, output, rows, cols, epsilon, dtype, stream);
 }

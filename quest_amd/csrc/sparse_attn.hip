@@ -30,6 +30,7 @@ using namespace quest;
 
 struct quest_decode_handler {
     uint32_t layout = 0;
+    uint32_t dtype = QUEST_DTYPE_F16;  // element type of the pools / q / o this handler serves (quest_decode_set_dtype)
     bool started = false;
     uint32_t n_sel = 0, num_qo_heads = 0, num_kv_heads = 0, head_dim = 0, page_size = 0;
     uint32_t pages_per_chunk = 0, n_chunks = 0;
@@ -157,6 +158,12 @@ extern "C" int quest_decode_set_selection_out(quest_decode_handler_t* h, void* v
     return 0;
 }
 
+extern "C" int quest_decode_set_dtype(quest_decode_handler_t* h, uint32_t dtype) {
+    if (!h || dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
+    h->dtype = dtype;
+    return 0;
+}
+
 extern "C" int quest_decode_set_batch(quest_decode_handler_t* h, uint32_t n_seqs) {
     if (!h || n_seqs == 0 || n_seqs > 65535u) return QUEST_EINVAL;  // grid.z limit
     h->batch = n_seqs;
@@ -271,6 +278,10 @@ enum class Route { kHeadLists, kSharedList, kLayer };  // which page lists the l
 // launch into the pools.
 static int check_request(const quest_decode_handler* h, DecodeRequest& r, Route route) {
     quest_paged_kv_t& kv = r.kv;
+    // element type first: an unknown value, a view that disagrees with the handler's type (quest_decode_set_dtype) or with the
+    // metadata view travelling in the same call
+    if (kv.dtype > QUEST_DTYPE_BF16 || (h && kv.dtype != h->dtype)) return QUEST_EINVAL;
+    if ((r.app_k || route == Route::kLayer) && r.metadata.dtype != kv.dtype) return QUEST_EINVAL;
     if (!h || r.batch.n_seqs == 0) return QUEST_EINVAL;
     if (r.state) kv.last_page_len = 1;  // placeholder; the kernel reads the real one from `state`
     if (!h->started) return QUEST_ESTATE;
@@ -456,9 +467,10 @@ static uint32_t grid_row_order(uint32_t chunks_per_head, uint32_t num_qo_heads, 
 // Behind every attention launch: the merge of a head's partials (it carries the armed step advance) or, for a plan
 // without a merge launch, the advance as a launch of its own.
 template <int D>
-static int merge_and_advance(quest_decode_handler* h, const DecodeParams& p, uint32_t heads_x_seqs, float* lse, hipStream_t s) {
+static int merge_and_advance(quest_decode_handler* h, const DecodeParams& p, uint32_t heads_x_seqs, float* lse, hipStream_t s,
+                             bool bf16) {
     if (p.n_chunks > 1 && !h->skip_merge) {  // o / lse / partials of a batch are contiguous over (sequence, head): one grid
-        hipLaunchKernelGGL((merge_states_kernel<D>), dim3(heads_x_seqs), dim3(D * kMergeGroups), 0, s, (const float*)p.ws, p.o,
+        hipLaunchKernelGGL((bf16 ? merge_states_kernel_bf16<D> : merge_states_kernel<D>), dim3(heads_x_seqs), dim3(D * kMergeGroups), 0, s, (const float*)p.ws, p.o,
                            lse, p.n_chunks, p.ws_stride, take_armed_advance(h));
         QUEST_LAUNCH_CHECK();
     }
@@ -467,7 +479,7 @@ static int merge_and_advance(quest_decode_handler* h, const DecodeParams& p, uin
 
 template <int D, int FC>
 static int launch_decode_fc(quest_decode_handler* h, const DecodeParams& p, uint32_t num_qo_heads, uint32_t waves,
-                            hipStream_t s, uint32_t n_seqs) {
+                            hipStream_t s, uint32_t n_seqs, bool bf16) {  // bf16: the *_bf16 kernels (the handler's element type)
     dim3 grid(h->n_chunks, num_qo_heads, n_seqs);
     const size_t lds = FC > 0 ? (size_t)p.ids_lds_offset + (p.stage_ids ? (size_t)((p.n_scores + 4u) & ~3u) * 4 : 0) : 0;  // the table has n_scores + 1 entries, staged in granules of 4
     // what this launch is (quest_decode_last_launch_info): keys per thread, waves, front-end variant, one-variant
@@ -487,9 +499,9 @@ static int launch_decode_fc(quest_decode_handler* h, const DecodeParams& p, uint
     if (p.vec_front == 8u) {  // tiles front end (choose_front_end: page size 16, 8 waves)
         if constexpr (FC == 8) {
             info[3] = 1u;
-            hipLaunchKernelGGL((sparse_decode_kernel<D, 16, 8, 8, 8>), grid, dim3(8 * kWave), 0, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
+            hipLaunchKernelGGL((bf16 ? sparse_decode_kernel_bf16<D, 16, 8, 8, 8> : sparse_decode_kernel<D, 16, 8, 8, 8>), grid, dim3(8 * kWave), 0, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
             QUEST_LAUNCH_CHECK();
-            return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s);
+            return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s, bf16);
         } else {
             return QUEST_EUNSUPPORTED;
         }
@@ -499,39 +511,39 @@ static int launch_decode_fc(quest_decode_handler* h, const DecodeParams& p, uint
         if constexpr (FC == 8 || FC == 16 || FC == 24 || FC == 32) {
             info[3] = 1u;
             if (p.vec_front == (uint32_t)VFA) {
-                hipLaunchKernelGGL((sparse_decode_kernel<D, 16, FC, 8, VFA>), grid, dim3(8 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
+                hipLaunchKernelGGL((bf16 ? sparse_decode_kernel_bf16<D, 16, FC, 8, VFA> : sparse_decode_kernel<D, 16, FC, 8, VFA>), grid, dim3(8 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
                 QUEST_LAUNCH_CHECK();
-                return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s);
+                return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s, bf16);
             }
             if (VFB != VFA && p.vec_front == (uint32_t)VFB) {
-                hipLaunchKernelGGL((sparse_decode_kernel<D, 16, FC, 8, VFB>), grid, dim3(8 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
+                hipLaunchKernelGGL((bf16 ? sparse_decode_kernel_bf16<D, 16, FC, 8, VFB> : sparse_decode_kernel<D, 16, FC, 8, VFB>), grid, dim3(8 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
                 QUEST_LAUNCH_CHECK();
-                return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s);
+                return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s, bf16);
             }
             info[3] = 0u;
         }
     }
     if (p.page_size == 16 && waves == 8)
-        hipLaunchKernelGGL((sparse_decode_kernel<D, 16, FC, 8>), grid, dim3(8 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
+        hipLaunchKernelGGL((bf16 ? sparse_decode_kernel_bf16<D, 16, FC, 8> : sparse_decode_kernel<D, 16, FC, 8>), grid, dim3(8 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
     else if (p.page_size == 16)
-        hipLaunchKernelGGL((sparse_decode_kernel<D, 16, FC, 4>), grid, dim3(4 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
+        hipLaunchKernelGGL((bf16 ? sparse_decode_kernel_bf16<D, 16, FC, 4> : sparse_decode_kernel<D, 16, FC, 4>), grid, dim3(4 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
     else
-        hipLaunchKernelGGL((sparse_decode_kernel<D, 0, FC, 4>), grid, dim3(4 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
+        hipLaunchKernelGGL((bf16 ? sparse_decode_kernel_bf16<D, 0, FC, 4> : sparse_decode_kernel<D, 0, FC, 4>), grid, dim3(4 * kWave), lds, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p);
     QUEST_LAUNCH_CHECK();
-    return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s);
+    return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, lse, s, bf16);
 }
 
 // fc: fused top-k front end variant (0 = page ids come from an index tensor)
 template <int D>
 static int launch_decode(quest_decode_handler* h, const DecodeParams& p, uint32_t num_qo_heads, int fc,
-                         uint32_t waves, hipStream_t s, uint32_t n_seqs) {
+                         uint32_t waves, hipStream_t s, uint32_t n_seqs, bool bf16) {
     switch (fc) {
-        case 0: return launch_decode_fc<D, 0>(h, p, num_qo_heads, waves, s, n_seqs);
-        case 8: return launch_decode_fc<D, 8>(h, p, num_qo_heads, waves, s, n_seqs);
-        case 16: return launch_decode_fc<D, 16>(h, p, num_qo_heads, waves, s, n_seqs);
-        case 24: return launch_decode_fc<D, 24>(h, p, num_qo_heads, waves, s, n_seqs);
-        case 32: return launch_decode_fc<D, 32>(h, p, num_qo_heads, waves, s, n_seqs);
-        case 64: return launch_decode_fc<D, 64>(h, p, num_qo_heads, waves, s, n_seqs);
+        case 0: return launch_decode_fc<D, 0>(h, p, num_qo_heads, waves, s, n_seqs, bf16);
+        case 8: return launch_decode_fc<D, 8>(h, p, num_qo_heads, waves, s, n_seqs, bf16);
+        case 16: return launch_decode_fc<D, 16>(h, p, num_qo_heads, waves, s, n_seqs, bf16);
+        case 24: return launch_decode_fc<D, 24>(h, p, num_qo_heads, waves, s, n_seqs, bf16);
+        case 32: return launch_decode_fc<D, 32>(h, p, num_qo_heads, waves, s, n_seqs, bf16);
+        case 64: return launch_decode_fc<D, 64>(h, p, num_qo_heads, waves, s, n_seqs, bf16);
         default: return QUEST_EUNSUPPORTED;
     }
 }
@@ -564,10 +576,11 @@ static int decode_entry(quest_decode_handler* h, DecodeRequest r, hipStream_t s)
     p.row_lead = fe.row_lead, p.fe2_prefilter = fe.fe2_prefilter, p.table_vec = fe.table_vec;
     p.budgets = r.state ? r.batch.page_budgets : nullptr;
     p.xcd_period = grid_row_order(h->n_chunks, r.num_qo_heads, p.group, r.batch.n_seqs == 1 ? &kv : nullptr);
+    const bool bf16 = h->dtype == QUEST_DTYPE_BF16;  // (check_request: the view's type is the handler's)
     switch (kv.head_dim) {
-        case 64: return launch_decode<64>(h, p, r.num_qo_heads, fe.fc, fe.waves, s, r.batch.n_seqs);
-        case 128: return launch_decode<128>(h, p, r.num_qo_heads, fe.fc, fe.waves, s, r.batch.n_seqs);
-        case 256: return launch_decode<256>(h, p, r.num_qo_heads, fe.fc, fe.waves, s, r.batch.n_seqs);
+        case 64: return launch_decode<64>(h, p, r.num_qo_heads, fe.fc, fe.waves, s, r.batch.n_seqs, bf16);
+        case 128: return launch_decode<128>(h, p, r.num_qo_heads, fe.fc, fe.waves, s, r.batch.n_seqs, bf16);
+        case 256: return launch_decode<256>(h, p, r.num_qo_heads, fe.fc, fe.waves, s, r.batch.n_seqs, bf16);
         default: return QUEST_EUNSUPPORTED;
     }
 }
@@ -575,6 +588,7 @@ static int decode_entry(quest_decode_handler* h, DecodeRequest r, hipStream_t s)
 template <int D>
 static int launch_shared(quest_decode_handler* h, DecodeParams p, uint32_t num_qo_heads, uint32_t gs, hipStream_t s,
                          uint32_t n_seqs) {
+    const bool bf16 = h->dtype == QUEST_DTYPE_BF16;  // (check_request: the view's type is the handler's)
     // (8-wave workgroups for group sizes 1 / 2 -- 16 waves per CU instead of 8, each with one page in flight -- measured
     // slower in round 4: cfg 2 18.4 vs 17.8 us per layer, the 32K dense kernel 94.4 vs 92.4 us)
     static const char* order_env = quest_tuning_env("QUEST_SHARED_HEADS_FIRST");  // unset: by layout
@@ -586,9 +600,9 @@ static int launch_shared(quest_decode_handler* h, DecodeParams p, uint32_t num_q
 #define QUEST_SHARED_CASE(GS)                                                                                                  \
     case GS:                                                                                                                   \
         if (p.app_k)                                                                                                           \
-            hipLaunchKernelGGL((shared_decode_kernel<D, GS, 4, true>), grid, block, 0, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p); \
+            hipLaunchKernelGGL((bf16 ? shared_decode_kernel_bf16<D, GS, 4, true> : shared_decode_kernel<D, GS, 4, true>), grid, block, 0, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p); \
         else                                                                                                                   \
-            hipLaunchKernelGGL((shared_decode_kernel<D, GS, 4, false>), grid, block, 0, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p); \
+            hipLaunchKernelGGL((bf16 ? shared_decode_kernel_bf16<D, GS, 4, false> : shared_decode_kernel<D, GS, 4, false>), grid, block, 0, s, QUEST_DECODE_HEAD_ARGS(p, num_qo_heads), p); \
         break;
     switch (gs) {
         QUEST_SHARED_CASE(1)
@@ -599,7 +613,7 @@ static int launch_shared(quest_decode_handler* h, DecodeParams p, uint32_t num_q
     }
 #undef QUEST_SHARED_CASE
     QUEST_LAUNCH_CHECK();
-    return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, p.lse, s);
+    return merge_and_advance<D>(h, p, num_qo_heads * n_seqs, p.lse, s, bf16);
 }
 
 static int shared_entry(quest_decode_handler* h, DecodeRequest r, hipStream_t s) {
@@ -758,6 +772,7 @@ extern "C" int quest_decode_layer_fused_batched(quest_decode_handler_t* h, const
     r.state = state, r.batch = batch;
     r.app_k = k, r.app_v = v, r.metadata = metadata;
     if (int e = check_request(h, r, Route::kLayer)) return e;
+    if (kv.dtype != QUEST_DTYPE_F16) return QUEST_EUNSUPPORTED;  // the one-launch layer has no bf16 form: the caller's two launches
     if (scores_out && score_stride < max_n_scores) return QUEST_EINVAL;
     if (batch.n_seqs > 1 && (batch.kv_table_stride < max_n_scores + 1 ||
                              (uint64_t)batch.meta_table_stride * metadata.page_size < max_n_scores))

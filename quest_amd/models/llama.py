@@ -244,7 +244,9 @@ class LlamaForCausalLM(nn.Module):
         ``model-0000x-of-0000y.safetensors`` + ``model.safetensors.index.json`` -- the way the reference does with
         ``LlamaForCausalLM.from_pretrained(...)`` (scripts/bench_textgen.py:53-58, evaluation/*).  Parameter names
         are HF's (``model.layers.N.self_attn.q_proj.weight`` ...), so tensors are copied by name, shard by shard,
-        straight to ``device``."""
+        straight to ``device``.  ``dtype``: float16 (default) or bfloat16 -- a bf16 checkpoint loads without a cast, and
+        with ``quest_init(dtype=torch.bfloat16)`` its KV cache, metadata and attention stay bf16 (the fused decode-layer
+        projections are fp16-only: a bf16 model's captured step takes the module path, ``fused_layers`` off)."""
         import json
         import os
 
@@ -285,8 +287,11 @@ class LlamaForCausalLM(nn.Module):
                         params[name].copy_(t)
                         if t.dtype != params[name].dtype and t.dtype in (torch.bfloat16, torch.float32) \
                                 and not bool(torch.isfinite(params[name]).all()):
-                            # e.g. a bf16 checkpoint whose values exceed fp16's range (the kernels are fp16 like the reference's)
-                            raise ValueError(f"{name}: {t.dtype} values overflow {params[name].dtype}")
+                            # e.g. a bf16 checkpoint whose values exceed fp16's range
+                            raise ValueError(f"{name}: {t.dtype} values overflow {params[name].dtype}. Load the checkpoint "
+                                             "in its own type with from_pretrained(dtype=torch.bfloat16) and give "
+                                             "quest_init / quest_init_batched the same dtype: the attention kernels "
+                                             "run bf16 pools natively.")
                         seen.add(name)
         missing = set(params) - seen
         if missing == {"lm_head.weight"} and hf.get("tie_word_embeddings", False):

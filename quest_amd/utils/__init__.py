@@ -181,10 +181,10 @@ def decode_topk_sparse_attn(q: torch.Tensor, estimated_attn_score: torch.Tensor,
 #     per token:  fill q/k/v buffers; g.replay(); ctl.prepare_metadata(1)   # host mirror only
 
 def score_scratch(controller) -> torch.Tensor:
-    """The fp16 page-score scratch of the state-driven launches: ``[Hq, stride]`` for an ``InferenceController``,
+    """The page-score scratch of the state-driven launches, in the controller's dtype (fp16 or bf16): ``[Hq, stride]`` for an ``InferenceController``,
     ``[n_seqs, Hq, stride]`` for a ``BatchedInferenceController``, with ``stride`` = the pool capacity in pages rounded
     up to 8 columns -- 16-byte aligned rows let the attention launch read a thread's 4 scores with one 8-byte
-    load (second-generation top-k front end, csrc/topk_bitmap.cuh).  Any ``[.., >= max_pages]`` fp16 tensor works;
+    load (second-generation top-k front end, csrc/topk_bitmap.cuh).  Any ``[.., >= max_pages]`` tensor of that dtype works;
     other strides take the first-generation front end (rows up to 4096 pages)."""
     stride = (controller.max_pages + 7) // 8 * 8
     # room for the rows' tile maxima behind the scores (long-row launches, ``decode_layer_dyn``); a batch gets it only
@@ -194,7 +194,7 @@ def score_scratch(controller) -> torch.Tensor:
     shape = (controller.num_heads, stride)
     if isinstance(controller, BatchedInferenceController):
         shape = (controller.n_seqs,) + shape
-    return torch.empty(shape, dtype=torch.float16, device=controller.device)
+    return torch.empty(shape, dtype=controller.dtype, device=controller.device)
 
 
 def _need_state(controller) -> None:

@@ -36,13 +36,20 @@ def _state_row(c: "InferenceController"):
             meta.indicies[-1], 0]
 
 
+def _make_handler(layout: int, dtype):
+    """A decode handler for pools of ``layout`` and ``dtype``: built the reference's way (fp16) unless the controller is
+    bf16, which is the handler's explicit extension."""
+    extra = {} if dtype == torch.float16 else {"dtype": dtype}
+    return BatchDecodeWithPagedKVCacheWrapper(kv_layout=TensorLayout.FORMAT2STR[layout], **extra)
+
+
 def _plan_graph_handlers(ctl, budget: int, dense_layers: bool) -> None:
     """Plan ``ctl``'s sparse handler for ``budget`` pages and, with ``dense_layers``, a second handler for full-KV layers
     over the per-sequence capacity -- once, for launches that will be replayed over many tokens."""
     plans = [(ctl._decode_handler, budget)]
     if dense_layers:
         if ctl._dense_handler is None:
-            ctl._dense_handler = BatchDecodeWithPagedKVCacheWrapper(kv_layout=TensorLayout.FORMAT2STR[ctl.layout])
+            ctl._dense_handler = _make_handler(ctl.layout, ctl.dtype)
         plans.append((ctl._dense_handler, ctl.max_pages))
     for handler, pages in plans:
         handler.set_batch(ctl.n_seqs)
@@ -57,6 +64,7 @@ class InferenceController:
     page_budgets = None
     one_launch_layers = False
     tiles_min_pages = TILES_MIN_PAGES
+    dtype = torch.float16  # element type of pools, handlers, top-k buffers and score scratch; the constructor's argument
 
     def __init__(self, num_layers, num_heads, head_dim, page_size,
                  page_budget,  # pages, including the last (current) page
@@ -82,7 +90,8 @@ class InferenceController:
                                       pool=metadata_pool)
 
         self._page_budget = page_budget
-        self._decode_handler = BatchDecodeWithPagedKVCacheWrapper(kv_layout=TensorLayout.FORMAT2STR[self.layout])
+        # (pools, handlers, top-k buffers and the score scratch all follow `dtype`: float16 or bfloat16)
+        self._decode_handler = _make_handler(self.layout, dtype)
         self._dense_handler = None  # planned by begin_graph_decode(dense_layers=True)
 
         self.kv_indices_with_last = None
@@ -248,6 +257,7 @@ class BatchedInferenceController:
     single-sequence path."""
 
     tiles_min_pages = TILES_MIN_PAGES
+    dtype = torch.float16  # element type of pools, handlers, top-k buffers and score scratch; the constructor's argument
 
     def __init__(self, n_seqs, num_layers, num_heads, head_dim, page_size, page_budget, max_seq_len, dtype, device,
                  num_kv_heads: Optional[int] = None, layout: int = TensorLayout.NHD,
@@ -271,7 +281,7 @@ class BatchedInferenceController:
         self.seqs = [InferenceController(num_layers, num_heads, head_dim, page_size, page_budget, max_seq_len, dtype,
                                          device, num_kv_heads=num_kv_heads, layout=layout, kv_pool=self.kv_pool,
                                          metadata_pool=self.metadata_pool) for _ in range(n_seqs)]
-        self._decode_handler = BatchDecodeWithPagedKVCacheWrapper(kv_layout=TensorLayout.FORMAT2STR[self.layout])
+        self._decode_handler = _make_handler(self.layout, dtype)
         self._dense_handler = None
         self.kv_tables = self.meta_tables = self.step_states = None
         self.state_epoch = 0
@@ -290,7 +300,9 @@ class BatchedInferenceController:
         # CUs) 13.27 / 13.01, 6: 12.03 / 12.47, 7: 11.64 / 11.96, 8: 11.15 / 11.60, 12 (1.5 per CU) 12.10 / 11.86, 16: 11.02 /
         # 11.16 (profiles/r05_sweep_sequences_per_gpu_one_vs_two_launches.txt).  With GQA the query heads of a group would
         # each stream their kv head's metadata (cfg 5: 68.9 vs 58.8 us per layer): two launches.
-        self.one_launch_layers = self.num_heads == self.num_kv_heads and self._fills_the_chip(n_seqs * num_heads, device)
+        # (fp16 only: the one-launch layer has no bf16 form -- quest_decode_layer_fused_batched returns QUEST_EUNSUPPORTED)
+        self.one_launch_layers = (dtype == torch.float16 and self.num_heads == self.num_kv_heads
+                                  and self._fills_the_chip(n_seqs * num_heads, device))
         self.last_layer_launches = None  # 1 / 2: which form utils.decode_layer_batched ran last (its docstring)
 
     @staticmethod

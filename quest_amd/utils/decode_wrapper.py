@@ -13,9 +13,13 @@ class BatchDecodeWithPagedKVCacheWrapper:
     """Owns the plan (pages per workgroup, partial-state workspace) that ``begin_forward`` makes
     once per decode step and every layer's ``forward`` reuses."""
 
-    def __init__(self, kv_layout: str = "NHD"):
+    def __init__(self, kv_layout: str = "NHD", dtype: torch.dtype = torch.float16):
+        """``dtype`` (EXTENSION): the element type of the pools / q / o the handler serves, float16 (the reference's only
+        one) or bfloat16."""
         self.kv_layout = kv_layout
-        self._wrapper = _kernels.BatchDecodeWithPagedKVCachePyTorchWrapper(TensorLayout.parse(kv_layout))
+        # (fp16: constructed with the reference's one-argument signature, which is all a drop-in binding of the reference has)
+        extra = {} if dtype == torch.float16 else {"dtype": dtype}
+        self._wrapper = _kernels.BatchDecodeWithPagedKVCachePyTorchWrapper(TensorLayout.parse(kv_layout), **extra)
 
     def begin_forward(self, indptr: torch.Tensor, num_qo_heads: int, num_kv_heads: int, head_dim: int,
                       page_size: int, data_type) -> None:

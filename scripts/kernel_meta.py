@@ -4,6 +4,8 @@ of the mangled name (template arguments read ILi128ELi16E...).
 
     python scripts/kernel_meta.py [substring ...]          (QUEST_HIP_LIB=<path> inspects another build)
     python scripts/kernel_meta.py --same-code OTHER.so     is every kernel's machine code (name, size, sha256) the same?
+    python scripts/kernel_meta.py --same-figures OTHER.so  do the kernels both libraries have keep their resources (VGPR, spills,
+                                                           scratch, LDS, SGPR, code bytes)?  Kernels only one of them has are counted.
 """
 import os
 import sys
@@ -21,6 +23,19 @@ if sys.argv[1:2] == ["--same-code"]:
     for n in diff:
         print(f"  {n[:100]} {a.get(n, ('-', '-'))[0]} {b.get(n, ('-', '-'))[0]}")
     sys.exit(1 if diff else 0)
+
+if sys.argv[1:2] == ["--same-figures"]:
+    mine, other = os.environ.get("QUEST_HIP_LIB") or LIB, sys.argv[2]
+    a, b = kernel_metadata(mine), kernel_metadata(other)
+    keys = ("vgpr", "vgpr_spill", "scratch", "lds", "sgpr", "code_bytes")
+    common = sorted(set(a) & set(b))
+    diff = [n for n in common if any(a[n][k] != b[n][k] for k in keys)]
+    print(f"{len(a)} kernels (src {library_hash(mine)}) vs {len(b)} (src {library_hash(other)}): {len(common)} in both, "
+          f"{len(set(a) - set(b))} only here, {len(set(b) - set(a))} only there; figures ({', '.join(keys)}) of the common ones: "
+          + ("all equal" if not diff else f"{len(diff)} differ"))
+    for n in diff:
+        print(f"  {n[:100]} {[a[n][k] for k in keys]} {[b[n][k] for k in keys]}")
+    sys.exit(1 if diff or set(b) - set(a) else 0)
 
 meta = kernel_metadata(os.environ.get("QUEST_HIP_LIB") or LIB)
 for name in sorted(meta):

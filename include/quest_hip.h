@@ -23,7 +23,7 @@
  *     bf16 differences: metadata max / min treat patterns above 0x7f80 as NaN, a new page's entry starts from -/+ the
  *     largest finite bf16 (0xff7f / 0x7f7f) instead of -/+65504, scores are bf16_rne of the same fp32 sum, partial
  *     attention states stay fp32.  fp16 only: the decode-layer projections (quest_decode_norm_gemv, _gemv_residual,
- *     _mlp_gate_up, _qkv_rope*) and quest_decode_layer_fused_batched, which returns QUEST_EUNSUPPORTED for bf16 views
+ *     _mlp_gate_up, _qkv_rope*, _qkv*) and quest_decode_layer_fused_batched, which returns QUEST_EUNSUPPORTED for bf16 views
  *     (the caller issues quest_append_estimate_batched + quest_decode_forward_fused_topk_batched).
  *   - Return value: 0 on success; a positive value is a hipError_t from a launch; a negative
  *     value is one of the QUEST_E* argument errors below.  quest_error_string() names both.
@@ -517,6 +517,19 @@ int quest_apply_rope_in_place_dtype(void* q, void* k, uint32_t n, uint32_t past_
                                     const float* inv_freq, float attention_factor, const quest_step_state_t* states,
                                     uint32_t dtype, quest_stream_t stream);
 
+/* Per-head RMSNorm of q and k fused with RoPE, in place, one launch (EXTENSION: Qwen3's q_norm / k_norm; the reference has
+ * no counterpart).  Rows, position sources, frequency sources and `dtype` as for quest_apply_rope_in_place_dtype;
+ * q_norm_weight / k_norm_weight: [head_dim] of the element type, shared by the heads.  Per head row, in fp32:
+ * inv = 1 / sqrtf(sum x^2 / head_dim + eps), n_d = x_d * inv * w_d, rotate-half RoPE on n, one round-to-nearest-even to
+ * the element type (transformers rounds after the normalisation, after the weight, and rounds cos / sin).
+ * QUEST_EINVAL before any launch for a NULL operand, an eps that is negative or not finite, an unknown dtype or a bad
+ * table / rope_scale / rope_theta; QUEST_EUNSUPPORTED for a head_dim other than 64 / 128 / 256. */
+int quest_apply_qk_norm_rope_in_place_dtype(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
+                                            uint32_t num_kv_heads, uint32_t head_dim, const void* q_norm_weight,
+                                            const void* k_norm_weight, float eps, float rope_scale, float rope_theta,
+                                            const float* inv_freq, float attention_factor,
+                                            const quest_step_state_t* states, uint32_t dtype, quest_stream_t stream);
+
 /* rms_norm_forward (bsk_ops.h:29-32, rms_norm.cu:160-212). input/output: [rows][cols], weight [cols]. */
 int quest_rms_norm_forward(const void* input, const void* weight, void* output, uint32_t rows,
                            uint32_t cols, float epsilon, quest_stream_t stream);
@@ -593,6 +606,19 @@ int quest_decode_qkv_rope_batched_freqs(const void* h, const void* gamma, float 
                                         uint32_t num_kv_heads, uint32_t head_dim, const float* inv_freq,
                                         float attention_factor, const quest_step_state_t* states, uint32_t n_tokens,
                                         quest_stream_t stream);
+
+/* The q-k-v launch without the rotation (fp16), for models whose q and k pass a per-head norm before RoPE: RMSNorm(h) ->
+ * q = Wq x [q_rows], k = Wk x, v = Wv x [kv_rows], stored unrotated; quest_apply_qk_norm_rope_in_place_dtype follows.
+ * The same row-dots in the same order as quest_decode_qkv_rope* at head_dim <= 256: a lane of the batch-1 kernel adds a
+ * row's products in the same order whatever the workgroup shape, and the batched form (n_tokens <= 16) is planned with the
+ * rotating launch's LDS budget, so both take the same n-token kernel -- the one
+ * quest_decode_batched_plan(hidden, q_rows + 2 kv_rows, n_tokens, 1, ...) names -- and v is bit-identical.  (Beyond
+ * head_dim 256 the rotating launch always takes the inputs-from-L2 kernel.) */
+int quest_decode_qkv(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
+                     void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows, quest_stream_t stream);
+int quest_decode_qkv_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
+                             void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows,
+                             uint32_t n_tokens, quest_stream_t stream);
 
 /* Which kernel an n-token launch of this shape takes (tests / tuning; nothing is launched): 1 and info = {k slices per
  * quad of rows, rounds, dynamic LDS bytes, workgroups, 128-wide k steps per row, weight fragments per set} for the persistent

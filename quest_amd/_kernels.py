@@ -188,6 +188,35 @@ def apply_rope_in_place_freqs(q, k, inv_freq, attention_factor: float, past_kv_l
           "apply_rope_in_place_freqs")
 
 
+def apply_qk_norm_rope_in_place(q, k, q_weight, k_weight, eps: float, past_kv_len: int = 0, rope_scale: float = 1.0,
+                                rope_theta: float = 1e4, inv_freq=None, attention_factor: float = 1.0, states=None) -> None:
+    """Per-head RMSNorm of q ``[N, Hq, D]`` / k ``[N, Hkv, D]`` (weights ``[D]``, shared by the heads, Qwen3's ``q_norm`` /
+    ``k_norm``) fused with RoPE, in place, one launch (EXTENSION).  Frequencies: ``inv_freq`` None = the ``rope_scale`` /
+    ``rope_theta`` formula, else the table of ``apply_rope_in_place_freqs``; positions: ``states`` None = row i at
+    ``past_kv_len + i``, else ``states`` ``[N, 8]`` int32 step states and row i at ``states[i].seq_len - 1``.  One element
+    type per call: q, k and both weights."""
+    for t, name in ((q, "q"), (k, "k"), (q_weight, "q_weight"), (k_weight, "k_weight")):
+        _check_input(t, name)
+    _check_dim(3, q, "q")
+    _check_dim(3, k, "k")
+    _check_eq(q.size(0), k.size(0), "q.size(0), k.size(0)")
+    _check_eq(q.size(2), k.size(2), "q.size(2), k.size(2)")
+    _check_half(q, "apply_qk_norm_rope_in_place", k, q_weight, k_weight)
+    for w, name in ((q_weight, "q_weight"), (k_weight, "k_weight")):
+        _check_eq(tuple(w.shape), (q.size(2),), f"{name}.shape, (head_dim,)")
+    if inv_freq is not None:
+        _check_rope_table(inv_freq, q.size(2))
+    if states is not None:
+        _check_input(states, "states")
+        _check_eq(states.dtype, torch.int32, "states.scalar_type(), torch::kInt32")
+        _check_eq(states.numel(), q.size(0) * STEP_STATE_INTS, "states.numel(), n * 8")
+    check(lib.quest_apply_qk_norm_rope_in_place_dtype(
+        q.data_ptr(), k.data_ptr(), q.size(0), int(past_kv_len), q.size(1), k.size(1), q.size(2), q_weight.data_ptr(),
+        k_weight.data_ptr(), float(eps), float(rope_scale), float(rope_theta),
+        inv_freq.data_ptr() if inv_freq is not None else None, float(attention_factor),
+        states.data_ptr() if states is not None else None, _DTYPES[q.dtype], _stream(q)), "apply_qk_norm_rope_in_place")
+
+
 def rms_norm_forward(input, weight, output, epsilon: float) -> None:
     """rms_norm.cu:183-212.  input/output ``[1, N, C]``, weight ``[C]``."""
     _check_input(input, "input")
@@ -375,9 +404,9 @@ def decode_mlp_gate_up(h, gamma, eps: float, w_gate, w_up, act) -> None:
                                        act.data_ptr(), hidden, inter, _stream(h)), "decode_mlp_gate_up")
 
 
-def _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim: int, state, n: int):
-    """Validation and leading C arguments shared by the four ``decode_qkv_rope*`` launches; ``n`` tokens, ``state`` their
-    step state(s) ``[n, 8]`` int32."""
+def _qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n: int):
+    """Validation and leading C arguments shared by every q/k/v projection launch (``decode_qkv*``, ``decode_qkv_rope*``);
+    ``n`` tokens."""
     hidden = wq.size(1)
     _check_mat(h, n, hidden, "h")
     _check_vec(gamma, hidden, "gamma")
@@ -387,11 +416,18 @@ def _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim: int, state, n: 
     _check_mat(q, n, wq.size(0), "q")
     _check_mat(k, n, wk.size(0), "k")
     _check_mat(v, n, wk.size(0), "v")
+    return (h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(), wk.data_ptr(), wv.data_ptr(), q.data_ptr(),
+            k.data_ptr(), v.data_ptr(), hidden)
+
+
+def _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim: int, state, n: int):
+    """``_qkv_args`` plus what the four rotating ``decode_qkv_rope*`` launches add: ``state`` = the tokens' step state(s)
+    ``[n, 8]`` int32, heads counted in ``head_dim``."""
+    args = _qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n)
     _check_input(state, "state")
     _check_eq(state.numel(), n * STEP_STATE_INTS, "states.numel(), n * 8")
     _check_eq(wq.size(0) % head_dim, 0, "wq.size(0) % head_dim, 0")
-    return (h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(), wk.data_ptr(), wv.data_ptr(), q.data_ptr(),
-            k.data_ptr(), v.data_ptr(), hidden, wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim))
+    return args + (wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim))
 
 
 def decode_qkv_rope(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, rope_scale: float, rope_theta: float,
@@ -410,6 +446,13 @@ def decode_qkv_rope_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: i
     _check_rope_table(inv_freq, head_dim)
     check(lib.quest_decode_qkv_rope_freqs(*args, inv_freq.data_ptr(), float(attention_factor), state.data_ptr(),
                                           _stream(h)), "decode_qkv_rope_freqs")
+
+
+def decode_qkv(h, gamma, eps: float, wq, wk, wv, q, k, v) -> None:
+    """q ``[1, Hq, D]``, k / v ``[1, Hkv, D]`` = projections of ``rmsnorm(h; gamma, eps)``, NOT rotated: the q-k-v launch of
+    models with a per-head q/k norm, which ``apply_qk_norm_rope_in_place`` follows."""
+    check(lib.quest_decode_qkv(*_qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, 1), wq.size(0), wk.size(0), _stream(h)),
+          "decode_qkv")
 
 
 # ---- the fused decode-layer launches for n <= 16 tokens (one per sequence of a batch)
@@ -484,6 +527,14 @@ def decode_qkv_rope_batched_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, hea
     _check_rope_table(inv_freq, head_dim)
     check(lib.quest_decode_qkv_rope_batched_freqs(*args, inv_freq.data_ptr(), float(attention_factor), states.data_ptr(),
                                                   n, _stream(h)), "decode_qkv_rope_batched_freqs")
+
+
+def decode_qkv_batched(h, gamma, eps: float, wq, wk, wv, q, k, v) -> None:
+    """``decode_qkv`` for n <= 16 tokens: h ``[n, hidden]``, q ``[n, Hq, D]``, k / v ``[n, Hkv, D]``."""
+    n = h.numel() // wq.size(1)
+    _check_tokens(n)
+    check(lib.quest_decode_qkv_batched(*_qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n), wq.size(0), wk.size(0), n,
+                                       _stream(h)), "decode_qkv_batched")
 
 
 # ---- state-driven (graph-replayable) forms: EXTENSIONS, see include/quest_hip.h quest_step_state_t.  One launch serves

@@ -562,6 +562,11 @@ struct PersistPlan {
     uint32_t vpp_magic;       // ceil(2^32 / (16 spp)): e / (16 spp) = umulhi(e, magic) for e < 2^16
 };
 
+// dynamic LDS a workgroup may ask for: the CU's 160 KiB less the kernel's static arrays (s_part 2 TG KiB, the rotation table
+// 4 TG KiB, s_ssq <= 1 KiB, s_inv) and some slack -- persist_kernel checks the sum at compile time
+constexpr size_t kCuLdsBytes = 160 * 1024;
+constexpr size_t persist_lds_budget(uint32_t tg, bool rope) { return (size_t)(158 - tg * (2 + (rope ? 4 : 0))) * 1024; }
+
 template <int MODE, int TG, int CM>
 __global__ __launch_bounds__(kPsWaves* kWave, 4) void persist_kernel(SkinnyArgs a, PersistPlan pl) {
     const GemvArgs& p = a.g;
@@ -569,11 +574,14 @@ __global__ __launch_bounds__(kPsWaves* kWave, 4) void persist_kernel(SkinnyArgs 
     extern __shared__ __attribute__((aligned(16))) unsigned char ps_smem[];
     half_t* x_s = reinterpret_cast<half_t*>(ps_smem);  // [4 TG][x_row] (normalised) inputs
     __shared__ float s_inv[4 * TG];
+    __shared__ float s_ssq[kXV][kPsWaves][2];  // RMSNorm prologue: per (input slot, wave) the sums of squares of its two tokens
     __shared__ float s_part[2][kPsWaves][4][4 * TG];  // [buffer][wave = quad slot x slice][row of the quad][token]
     // kGvQkvRope: (cos, sin) of every (token, frequency), computed once per workgroup while the first weights are on their
     // way; a round's epilogue reads it (no sincosf, with its large-argument path, per round)
     constexpr int kRopeMaxHalfD = 128;
     __shared__ float2 s_rope[MODE == kGvQkvRope ? 4 * TG * kRopeMaxHalfD : 1];
+    static_assert(sizeof(s_inv) + sizeof(s_ssq) + sizeof(s_part) + sizeof(s_rope) + persist_lds_budget(TG, MODE == kGvQkvRope)
+                      <= kCuLdsBytes, "static arrays + the largest dynamic request must fit the CU's LDS");
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
     const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
 #ifdef QUEST_PS_TIMELINE  // tuning build: s_memtime stamps of (workgroup 0 | last, wave 0 | 15) -> p.out[2] (16 x 4 x int64)
@@ -662,9 +670,12 @@ __global__ __launch_bounds__(kPsWaves* kWave, 4) void persist_kernel(SkinnyArgs 
 
     __builtin_amdgcn_s_barrier();
     PS_STAMP();
-    if (norm) {  // 1 / rms per token: a thread's vector i lies in ONE token; per-token totals through LDS atomics
-        if (tid < 4u * TG) s_inv[tid] = 0.f;
-        __syncthreads();
+    if (norm) {
+        // 1 / rms per token.  A thread's vector i lies in ONE token and the lanes of a wave hold at most two tokens
+        // (vpp >= 64): every (slot i, wave) leaves the sums of its two sides t0, t0 + 1 in LDS, and wave t adds token t's
+        // entries in a FIXED order -- the result does not depend on the order in which the waves arrive (per-token LDS
+        // atomics did: two launches over the same inputs, or two workgroups of one launch, could normalise a token with
+        // 1 / rms values one fp32 ulp apart, and then differ in the fp16 rounding of an input).
 #pragma unroll
         for (int i = 0; i < kXV; ++i) {
             const uint32_t e = tid + (uint32_t)i * kPsWaves * kWave, t = __umulhi(e, pl.vpp_magic);
@@ -674,14 +685,21 @@ __global__ __launch_bounds__(kPsWaves* kWave, 4) void persist_kernel(SkinnyArgs 
 #pragma unroll
                 for (int c = 0; c < kVec; ++c) ss = __builtin_fmaf(xf[c], xf[c], ss);
             }
-            // lanes of a wave hold at most two tokens (vpp >= 64): reduce each side, one atomic per side
             const uint32_t t0 = __builtin_amdgcn_readfirstlane(t);
             const float s_lo = wave_allreduce_sum(t == t0 ? ss : 0.f, (int)lane), s_hi = wave_allreduce_sum(t == t0 ? 0.f : ss, (int)lane);
-            if (lane == 0 && t0 < 4u * TG) atomicAdd(&s_inv[t0], s_lo);
-            if (lane == 0 && t0 + 1u < 4u * TG) atomicAdd(&s_inv[t0 + 1u], s_hi);
+            if (lane == 0) s_ssq[i][wave][0] = s_lo, s_ssq[i][wave][1] = s_hi;
         }
         __syncthreads();
-        if (tid < 4u * TG) s_inv[tid] = 1.0f / sqrtf(s_inv[tid] / (float)p.in_dim + p.eps);
+        if (wave < 4u * TG) {  // wave-uniform: wave t owns token t
+            float tot = 0.f;
+            for (uint32_t idx = lane; idx < (uint32_t)kXV * kPsWaves * 2u; idx += kWave) {
+                const uint32_t i = idx / (kPsWaves * 2u), w = (idx >> 1) % kPsWaves, side = idx & 1u;
+                const uint32_t tt = __umulhi(w * kWave + i * kPsWaves * kWave, pl.vpp_magic) + side;  // = that wave's t0 (+ 1)
+                tot += tt == wave ? s_ssq[i][w][side] : 0.f;
+            }
+            tot = wave_allreduce_sum(tot, (int)lane);
+            if (lane == 0) s_inv[wave] = 1.0f / sqrtf(tot / (float)p.in_dim + p.eps);
+        }
         __syncthreads();
     }
     x_store(x_s);
@@ -793,15 +811,12 @@ __global__ __launch_bounds__(kPsWaves* kWave, 4) void persist_kernel(SkinnyArgs 
 #endif
 }
 
-// dynamic LDS a workgroup may ask for: the CU's 160 KiB less the kernel's static arrays (s_part 2 TG KiB, the rotation table
-// 4 TG KiB) and some slack
 constexpr int kMaxDevices = 64;
 static int current_device() {  // index into the per-device caches below; -1: unknown (no caching)
     int dev = -1;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= kMaxDevices) return -1;
     return dev;
 }
-static size_t persist_lds_budget(uint32_t tg, bool rope) { return (size_t)(158 - tg * (2 + (rope ? 4 : 0))) * 1024; }
 
 template <int MODE, int TG>
 static int launch_persist_tg(const SkinnyArgs& a, const PersistPlan& pl, uint32_t grid, size_t lds, hipStream_t s) {
@@ -866,8 +881,10 @@ static bool plan_persist(const SkinnyArgs& a, uint32_t virtual_rows, uint32_t tg
 static uint32_t token_groups(uint32_t n_tokens) { return n_tokens <= 4 ? 1 : (n_tokens <= 8 ? 2 : 4); }
 
 // QUEST_BATCHED_GEMV=skinny forces the first kernel (tuning / tests).
+// plan_as_rope: plan with the rotating q/k/v launch's (smaller) LDS budget, so that the unrotated q/k/v launch takes the
+// same n-token kernel as the rotating one at every shape (its v is then the same bits)
 template <int MODE>
-static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_t s) {
+static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_t s, bool plan_as_rope = false) {
     if (a.n_tokens == 0 || a.n_tokens > 16) return QUEST_EINVAL;
     if (a.g.in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
     static const bool force_skinny = [] {
@@ -879,7 +896,7 @@ static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_
     uint32_t grid = 0;
     size_t lds = 0;
     if (MODE == kGvQkvRope && a.g.head_dim > 256) return launch_skinny<MODE>(a, virtual_rows, s);  // (the LDS rotation table)
-    if (!force_skinny && plan_persist(a, virtual_rows, tg, MODE == kGvQkvRope, pl, grid, lds)) {
+    if (!force_skinny && plan_persist(a, virtual_rows, tg, MODE == kGvQkvRope || plan_as_rope, pl, grid, lds)) {
         if (tg == 1) return launch_persist_tg<MODE, 1>(a, pl, grid, lds, s);
         if (tg == 2) return launch_persist_tg<MODE, 2>(a, pl, grid, lds, s);
         return launch_persist_tg<MODE, 4>(a, pl, grid, lds, s);
@@ -987,6 +1004,29 @@ extern "C" int quest_decode_qkv_rope_freqs(const void* h, const void* gamma, flo
                     {1.0f, 0.f, inv_freq, attention_factor}, state, false, 0, stream);
 }
 
+// q, k, v projections WITHOUT the rotation (models with a per-head q/k norm between the projection and RoPE: the norm
+// needs a whole head row, which this launch spreads over several workgroups -- quest_apply_qk_norm_rope_in_place_dtype
+// follows as a launch of its own).  The plain launch with three matrices: the same row-dots in the same k order as
+// quest_decode_qkv_rope*, the epilogue stores them as they are.
+static GemvArgs qkv_args(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
+                         void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows) {
+    GemvArgs p = plain_args(h, gamma, eps, wq, q, hidden, q_rows);
+    p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
+    p.rows[1] = p.rows[2] = kv_rows;
+    p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
+    return p;
+}
+
+extern "C" int quest_decode_qkv(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
+                                void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows,
+                                quest_stream_t stream) {
+    if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v) return QUEST_EINVAL;
+    if (hidden == 0 || q_rows == 0 || kv_rows == 0) return QUEST_EINVAL;
+    if (hidden % 8 != 0) return QUEST_EUNSUPPORTED;
+    return launch_gemv<kGvPlain>(qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows), q_rows + 2 * kv_rows,
+                                 (hipStream_t)stream);
+}
+
 // ---- the same for n_tokens <= 16 decode tokens (x: [n_tokens][in_dim], outputs [n_tokens][out_dim], contiguous)
 extern "C" int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out,
                                               uint32_t in_dim, uint32_t out_dim, uint32_t n_tokens, quest_stream_t stream) {
@@ -1032,6 +1072,16 @@ extern "C" int quest_decode_qkv_rope_batched_freqs(const void* h, const void* ga
     if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
     return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
                     {1.0f, 0.f, inv_freq, attention_factor}, states, true, n_tokens, stream);
+}
+
+extern "C" int quest_decode_qkv_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+                                        const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows,
+                                        uint32_t kv_rows, uint32_t n_tokens, quest_stream_t stream) {
+    if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v) return QUEST_EINVAL;
+    if (hidden == 0 || q_rows == 0 || kv_rows == 0) return QUEST_EINVAL;
+    SkinnyArgs a = skinny_args(qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows), n_tokens);
+    a.out_stride[1] = a.out_stride[2] = kv_rows;
+    return launch_batched<kGvPlain>(a, q_rows + 2 * kv_rows, (hipStream_t)stream, true);
 }
 
 // Which kernel an n-token launch of this shape takes (tests / tuning; no launch): returns 1 and fills

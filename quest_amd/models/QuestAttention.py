@@ -29,27 +29,40 @@ class QuestAttention(nn.Module):
         self.config = config
         self.hidden_size = config.hidden_size
         self.num_heads = config.num_attention_heads
-        self.head_dim = self.hidden_size // self.num_heads
+        # the config's own head_dim where it has one (Qwen3, Mistral-Nemo: heads x head_dim != hidden_size)
+        self.head_dim = qrope.head_dim_of(config)
         self.num_key_value_heads = getattr(config, "num_key_value_heads", self.num_heads)
         self.num_key_value_groups = self.num_heads // self.num_key_value_heads
         self.max_position_embeddings = getattr(config, "max_position_embeddings", None)
         self.fused = fused
-        if self.head_dim * self.num_heads != self.hidden_size:
+        if getattr(config, "head_dim", None) is None and self.head_dim * self.num_heads != self.hidden_size:
             raise ValueError(f"hidden_size must be divisible by num_heads (got `hidden_size`: {self.hidden_size}"
                              f" and `num_heads`: {self.num_heads}).")
         self.q_proj = nn.Linear(self.hidden_size, self.num_heads * self.head_dim, bias=False)
         self.k_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=False)
         self.v_proj = nn.Linear(self.hidden_size, self.num_key_value_heads * self.head_dim, bias=False)
         self.o_proj = nn.Linear(self.num_heads * self.head_dim, self.hidden_size, bias=False)
+        # Qwen3: RMSNorm over each head's q and k vector before RoPE (weights [head_dim], shared by the heads; HF names
+        # self_attn.q_norm.weight / k_norm.weight).  Never run as modules: the fused norm + RoPE launch reads the weights.
+        self.qk_norm = bool(getattr(config, "qk_norm", False))
+        if self.qk_norm:
+            from .llama import LlamaRMSNorm
+
+            if self.head_dim not in (64, 128, 256):  # the norm has no other implementation to fall back to
+                raise ValueError(f"head_dim = {self.head_dim}: the per-head q/k norm + RoPE launch serves head_dim 64, 128 "
+                                 "and 256")
+
+            self.q_norm = LlamaRMSNorm(self.head_dim, config.rms_norm_eps)
+            self.k_norm = LlamaRMSNorm(self.head_dim, config.rms_norm_eps)
         # rope: default theta 1e4.  Default and linear position interpolation run the kernels' formula, as in the
-        # reference kernel path (QuestAttention.py:40-51); llama3 and yarn scaling the kernels' frequency table
-        # (models/rope.py), held in `rope_freqs` = (device inv_freq, attention_factor) -- NOT a buffer: it must survive
+        # reference kernel path (QuestAttention.py:40-51); llama3 and yarn scaling -- and the default RoPE of the model
+        # types after Llama -- the kernels' frequency table (models/rope.py), held in `rope_freqs` = (device inv_freq, attention_factor) -- NOT a buffer: it must survive
         # the meta-device construction of from_pretrained, stay out of the state_dict and stay fp32 under .half()
         scaling = getattr(config, "rope_scaling", None)
         kind = qrope.rope_type(scaling)
         self.rope_scale = float(scaling["factor"]) if kind == "linear" else 1.0
         self.rope_theta = float(getattr(config, "rope_theta", 1e4))
-        self.rope_table = kind in qrope.TABLE_TYPES
+        self.rope_table = qrope.takes_table(config)
         self.rope_freqs = None  # set by LlamaForCausalLM.quest_init* (one table for all layers), else on first use
 
     def rotary(self, device):
@@ -58,6 +71,12 @@ class QuestAttention(nn.Module):
         if self.rope_table and (self.rope_freqs is None or self.rope_freqs[0].device != device):
             self.rope_freqs = qrope.device_rope_parameters(self.config, device)
         return self.rope_freqs
+
+    def qk_norm_args(self):
+        """The ``qk_norm`` argument of the ``quest_amd.utils`` launches: None or (q weight, k weight, eps)."""
+        if not self.qk_norm:
+            return None
+        return self.q_norm.weight, self.k_norm.weight, self.q_norm.variance_epsilon
 
     def forward(self, hidden_states: torch.Tensor, attention_mask: Optional[torch.Tensor] = None,
                 position_ids: Optional[torch.LongTensor] = None, past_key_value: Optional[Tuple[torch.Tensor]] = None,
@@ -76,8 +95,13 @@ class QuestAttention(nn.Module):
         nvtx.range_pop()
 
         nvtx.range_push("RoPE")
-        qutils.apply_rope_in_place(q, k, iController.kv_cache.seqlen - q_len, rope_scale=self.rope_scale,
-                                   rope_theta=self.rope_theta, rope_freqs=self.rotary(q.device))
+        if self.qk_norm:
+            qutils.apply_qk_norm_rope_in_place(q, k, iController.kv_cache.seqlen - q_len, *self.qk_norm_args(),
+                                               rope_scale=self.rope_scale, rope_theta=self.rope_theta,
+                                               rope_freqs=self.rotary(q.device))
+        else:
+            qutils.apply_rope_in_place(q, k, iController.kv_cache.seqlen - q_len, rope_scale=self.rope_scale,
+                                       rope_theta=self.rope_theta, rope_freqs=self.rotary(q.device))
         nvtx.range_pop()
 
         if q_len > 1:
@@ -122,7 +146,7 @@ class QuestAttention(nn.Module):
             raise ValueError(f"`attn_output` should be of size {(bsz, q_len, self.num_heads, self.head_dim)}, but is"
                              f" {attn.size()}")
         nvtx.range_push("o_proj")
-        out = self.o_proj(attn.reshape(bsz, q_len, self.hidden_size))
+        out = self.o_proj(attn.reshape(bsz, q_len, self.num_heads * self.head_dim))
         nvtx.range_pop()
         return out, None, past_key_value
 
@@ -140,8 +164,10 @@ class QuestAttention(nn.Module):
         v = self.v_proj(hidden_states).view(n, self.num_key_value_heads, self.head_dim)
         if dense:
             attn = qutils.decode_layer_dense_batched(q, k, v, controller, self.layer_idx, self.rope_scale,
-                                                     self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device))
+                                                     self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device),
+                                                     qk_norm=self.qk_norm_args())
         else:
             attn = qutils.decode_layer_batched(q, k, v, controller, self.layer_idx, scores, self.rope_scale,
-                                               self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device))
-        return self.o_proj(attn.reshape(n, 1, self.hidden_size))
+                                               self.rope_theta, apply_rope=True, rope_freqs=self.rotary(q.device),
+                                               qk_norm=self.qk_norm_args())
+        return self.o_proj(attn.reshape(n, 1, self.num_heads * self.head_dim))

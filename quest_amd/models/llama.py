@@ -1,4 +1,4 @@
-"""Llama-architecture decoder that threads an ``InferenceController`` through ``QuestAttention``.
+"""Llama-architecture decoder (Llama, Mistral, Qwen3 dense) that threads an ``InferenceController`` through ``QuestAttention``.
 
 The reference ships a fork of HF's modeling_llama (quest/models/llama.py, 835 lines) whose only
 Quest-specific parts are: ``quest_init`` / ``quest_clear`` (:520-560), the per-forward controller
@@ -35,36 +35,62 @@ class LlamaConfig:
     max_position_embeddings: int = 32768
     rope_scaling: Optional[dict] = None
     rope_theta: float = 1e4
+    head_dim: Optional[int] = None   # None: hidden_size // num_attention_heads (Qwen3, Mistral-Nemo set their own)
+    qk_norm: bool = False            # Qwen3: RMSNorm over each head's q and k vector before RoPE
+    model_type: str = "llama"        # "llama", "mistral" or "qwen3": what to_hf_dict / save_pretrained write back
 
     def __post_init__(self):
         if self.num_key_value_heads is None:
             self.num_key_value_heads = self.num_attention_heads
+        if self.model_type not in _ARCHITECTURES:
+            raise ValueError(f"model_type = {self.model_type!r}: supported are {sorted(_ARCHITECTURES)}")
 
     # ---- Hugging Face config.json <-> LlamaConfig (the fields the Quest path reads; quest/models/llama.py takes the
     # whole HF LlamaConfig, of which it uses exactly these)
     @classmethod
     def from_hf_dict(cls, d: dict) -> "LlamaConfig":
-        if d.get("model_type", "llama") != "llama":
-            raise ValueError(f"not a Llama checkpoint: model_type = {d.get('model_type')!r}")
+        model_type = d.get("model_type", "llama")
+        if model_type not in _ARCHITECTURES:
+            moe = " (mixture-of-experts models are not supported)" if "moe" in str(model_type) or model_type == "mixtral" else ""
+            raise ValueError(f"model_type = {model_type!r} is not supported{moe}: the decoder serves "
+                             f"{sorted(_ARCHITECTURES)} (Llama arithmetic, for qwen3 with the per-head q/k norm)")
         rope = d.get("rope_parameters") or {}        # transformers >= 5 nests theta / scaling here
         scaling = d.get("rope_scaling")
         if scaling is None and rope.get("rope_type", "default") not in ("default", None):
             scaling = {k: v for k, v in rope.items() if k != "rope_theta"}
         if float(d.get("partial_rotary_factor", rope.get("partial_rotary_factor", 1.0))) != 1.0:
             raise ValueError("partial rotary embeddings (partial_rotary_factor != 1) are not supported")
-        if d.get("attention_bias") or d.get("mlp_bias"):
-            raise ValueError("bias terms are not part of the reference's Llama fork")
+        for field in ("attention_bias", "mlp_bias"):
+            if d.get(field):
+                raise ValueError(f"{field} = true: bias terms are not part of the reference's Llama fork")
+        # sliding-window attention is not built: the paged kernels attend the whole cache
+        if d.get("use_sliding_window"):
+            raise ValueError("use_sliding_window = true: sliding-window attention is not supported")
+        if d.get("sliding_window") is not None and d.get("use_sliding_window", True):
+            raise ValueError(f"sliding_window = {d['sliding_window']} is set and active: sliding-window attention is not "
+                             "supported (a checkpoint trained without it has sliding_window: null)")
+        other = sorted({t for t in (d.get("layer_types") or []) if t != "full_attention"})
+        if other:
+            raise ValueError(f"layer_types holds {other}: only 'full_attention' layers are supported")
         head_dim = d.get("head_dim")
-        if head_dim is not None and head_dim * d["num_attention_heads"] != d["hidden_size"]:
-            raise ValueError("head_dim * num_attention_heads != hidden_size is not supported (QuestAttention.py:24-29)")
         return cls(vocab_size=d["vocab_size"], hidden_size=d["hidden_size"], intermediate_size=d["intermediate_size"],
                    num_hidden_layers=d["num_hidden_layers"], num_attention_heads=d["num_attention_heads"],
                    num_key_value_heads=d.get("num_key_value_heads"), rms_norm_eps=d.get("rms_norm_eps", 1e-5),
                    max_position_embeddings=d.get("max_position_embeddings", 32768), rope_scaling=scaling,
-                   rope_theta=float(d.get("rope_theta", rope.get("rope_theta", 1e4))))
+                   rope_theta=float(d.get("rope_theta", rope.get("rope_theta", 1e4))),
+                   head_dim=int(head_dim) if head_dim is not None else None, qk_norm=model_type == "qwen3",
+                   model_type=model_type)
 
     def to_hf_dict(self, dtype: str = "float16", tie_word_embeddings: bool = False) -> dict:
-        return {"architectures": ["LlamaForCausalLM"], "model_type": "llama", "hidden_act": "silu",
+        extra = {}
+        if self.head_dim is not None:
+            extra["head_dim"] = self.head_dim
+        if self.model_type == "mistral":
+            extra["sliding_window"] = None  # (transformers' MistralConfig defaults to 4096)
+        elif self.model_type == "qwen3":
+            extra.update(sliding_window=None, use_sliding_window=False)
+        return {**extra, "architectures": [_ARCHITECTURES[self.model_type]], "model_type": self.model_type,
+                "hidden_act": "silu",
                 "attention_bias": False, "mlp_bias": False, "torch_dtype": dtype, "dtype": dtype,
                 "vocab_size": self.vocab_size, "hidden_size": self.hidden_size,
                 "intermediate_size": self.intermediate_size, "num_hidden_layers": self.num_hidden_layers,
@@ -72,6 +98,10 @@ class LlamaConfig:
                 "rms_norm_eps": self.rms_norm_eps, "max_position_embeddings": self.max_position_embeddings,
                 "rope_scaling": self.rope_scaling, "rope_theta": self.rope_theta,
                 "tie_word_embeddings": tie_word_embeddings}
+
+
+# model_type -> the transformers class that loads what save_pretrained writes
+_ARCHITECTURES = {"llama": "LlamaForCausalLM", "mistral": "MistralForCausalLM", "qwen3": "Qwen3ForCausalLM"}
 
 
 class LlamaRMSNorm(nn.Module):
@@ -116,19 +146,26 @@ class LlamaDecoderLayer(nn.Module):
 
     def forward_state_fused(self, h: torch.Tensor, controller, scores, dense: bool, ws: "DecodeWorkspace") -> torch.Tensor:
         """``forward_state`` in 4 launches besides the attention's: RMSNorm + q/k/v projections + RoPE, o_proj + residual,
-        RMSNorm + gate/up + SiLU*up, down_proj + residual (csrc/decode_layer.hip; EXTENSION).  ``h`` is the residual stream,
+        RMSNorm + gate/up + SiLU*up, down_proj + residual (csrc/decode_layer.hip; EXTENSION).  A model with a per-head q/k
+        norm (Qwen3) takes FIVE: the norm needs a whole head row, which the q/k/v launch spreads over several workgroups,
+        so that launch stores q, k, v unrotated and the q/k norm + RoPE launch follows.  ``h`` is the residual stream,
         updated IN PLACE; fp16.  An ``InferenceController`` takes the batch-1 launches (``h`` ``[hidden]``), a
         ``BatchedInferenceController`` the n-token ones at every n <= 16 (``h`` ``[n, hidden]``; the weights are read once
         per batch: persist_kernel) -- different kernels, whose results differ in the last bits."""
         a, m = self.self_attn, self.mlp
-        qkv_rope, qkv_rope_freqs, gemv_residual, mlp_gate_up = _fused_layer_launches(controller)[:4]
+        launches = _fused_layer_launches(controller)
+        qkv_rope, qkv_rope_freqs, gemv_residual, mlp_gate_up = launches[:4]
         freqs = a.rotary(h.device)
         qkv = (h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon, a.q_proj.weight, a.k_proj.weight,
-               a.v_proj.weight, ws.q, ws.k, ws.v, a.head_dim)
-        if freqs is None:
-            qkv_rope(*qkv, a.rope_scale, a.rope_theta, controller.step_states)
+               a.v_proj.weight, ws.q, ws.k, ws.v)
+        if a.qk_norm:
+            launches[5](*qkv)
+            qutils.apply_qk_norm_rope_in_place(ws.q, ws.k, 0, *a.qk_norm_args(), rope_scale=a.rope_scale,
+                                               rope_theta=a.rope_theta, rope_freqs=freqs, states=controller.step_states)
+        elif freqs is None:
+            qkv_rope(*qkv, a.head_dim, a.rope_scale, a.rope_theta, controller.step_states)
         else:
-            qkv_rope_freqs(*qkv, freqs[0], freqs[1], controller.step_states)
+            qkv_rope_freqs(*qkv, a.head_dim, freqs[0], freqs[1], controller.step_states)
         if dense:
             attn = qutils.decode_layer_dense_batched(ws.q, ws.k, ws.v, controller, a.layer_idx, out=ws.attn)
         else:
@@ -142,12 +179,13 @@ class LlamaDecoderLayer(nn.Module):
 
 def _fused_layer_launches(controller):
     """The projection launches of the fused decoder layer and of the final norm + lm_head for ``controller``'s kind: (q/k/v
-    + RoPE by formula, by frequency table, GEMV + residual, MLP gate/up, norm + GEMV)."""
+    + RoPE by formula, by frequency table, GEMV + residual, MLP gate/up, norm + GEMV, q/k/v unrotated)."""
     if isinstance(controller, qutils.BatchedInferenceController):
         return (_kernels.decode_qkv_rope_batched, _kernels.decode_qkv_rope_batched_freqs,
-                _kernels.decode_gemv_residual_batched, _kernels.decode_mlp_gate_up_batched, _kernels.decode_norm_gemv_batched)
+                _kernels.decode_gemv_residual_batched, _kernels.decode_mlp_gate_up_batched, _kernels.decode_norm_gemv_batched,
+                _kernels.decode_qkv_batched)
     return (_kernels.decode_qkv_rope, _kernels.decode_qkv_rope_freqs, _kernels.decode_gemv_residual,
-            _kernels.decode_mlp_gate_up, _kernels.decode_norm_gemv)
+            _kernels.decode_mlp_gate_up, _kernels.decode_norm_gemv, _kernels.decode_qkv)
 
 
 def fused_layer_launches_supported(config, n_tokens: int) -> bool:
@@ -155,12 +193,17 @@ def fused_layer_launches_supported(config, n_tokens: int) -> bool:
     so that a model outside them falls back to the module path (nn.Linear + separate norm / RoPE / activation launches)
     instead of failing inside the capture with QUEST_EUNSUPPORTED: input dimensions a multiple of 8 halves (16-byte
     vectors); the batch-1 kernels stage an input vector of at most 30720 halves in LDS (24576 with the RMSNorm prologue
-    of the n-token fallback kernel); RoPE pairs need head_dim % 4 == 0 (batch 1) / % 16 == 0 (n tokens)."""
+    of the n-token fallback kernel); RoPE pairs need head_dim % 4 == 0 (batch 1) / % 16 == 0 (n tokens).  o_proj reads
+    heads x head_dim inputs, which a config with its own head_dim makes differ from hidden_size; a per-head q/k norm
+    needs a head_dim its launch serves (64 / 128 / 256)."""
     hidden, inter = config.hidden_size, config.intermediate_size
-    head_dim = getattr(config, "head_dim", None) or hidden // config.num_attention_heads
-    if hidden % 8 or inter % 8 or head_dim % 4:
+    head_dim = rope_mod.head_dim_of(config)
+    attn_dim = config.num_attention_heads * head_dim
+    if hidden % 8 or inter % 8 or attn_dim % 8 or head_dim % 4:
         return False
-    if max(hidden, inter) > 30720:
+    if max(hidden, inter, attn_dim) > 30720:
+        return False
+    if getattr(config, "qk_norm", False) and head_dim not in (64, 128, 256):
         return False
     if n_tokens > 1 and (head_dim % 16 or hidden > 24576):
         return False
@@ -172,7 +215,7 @@ class DecodeWorkspace:
     (sequences of a batch) per step."""
 
     def __init__(self, config: LlamaConfig, dtype, device, n: int = 1):
-        d = config.hidden_size // config.num_attention_heads
+        d = rope_mod.head_dim_of(config)
         self.q = torch.empty(n, config.num_attention_heads, d, dtype=dtype, device=device)
         self.k = torch.empty(n, config.num_key_value_heads, d, dtype=dtype, device=device)
         self.v = torch.empty(n, config.num_key_value_heads, d, dtype=dtype, device=device)
@@ -240,7 +283,7 @@ class LlamaForCausalLM(nn.Module):
     @classmethod
     def from_pretrained(cls, path: str, device=torch.device("cuda:0"), dtype=torch.float16,
                         fused: bool = True) -> "LlamaForCausalLM":
-        """Load a Hugging Face Llama checkpoint directory -- ``config.json`` + ``model.safetensors`` or the sharded
+        """Load a Hugging Face Llama, Mistral or Qwen3 (dense) checkpoint directory -- ``config.json`` + ``model.safetensors`` or the sharded
         ``model-0000x-of-0000y.safetensors`` + ``model.safetensors.index.json`` -- the way the reference does with
         ``LlamaForCausalLM.from_pretrained(...)`` (scripts/bench_textgen.py:53-58, evaluation/*).  Parameter names
         are HF's (``model.layers.N.self_attn.q_proj.weight`` ...), so tensors are copied by name, shard by shard,
@@ -280,7 +323,7 @@ class LlamaForCausalLM(nn.Module):
                         if name.endswith("rotary_emb.inv_freq"):  # buffer of older HF exports; recomputed by the rope kernel
                             continue
                         if name not in params:
-                            raise KeyError(f"{fn}: unexpected tensor {name!r} (not a Llama decoder parameter)")
+                            raise KeyError(f"{fn}: unexpected tensor {name!r} (not a parameter of this decoder)")
                         t = sf.get_tensor(name)
                         if t.shape != params[name].shape:
                             raise ValueError(f"{name}: checkpoint shape {tuple(t.shape)} != model {tuple(params[name].shape)}")
@@ -303,7 +346,9 @@ class LlamaForCausalLM(nn.Module):
 
     def save_pretrained(self, path: str, max_shard_bytes: int = 4 << 30) -> None:
         """Write ``config.json`` + safetensors shard(s) in the Hugging Face layout (tensor names = HF's), so that
-        ``transformers.LlamaForCausalLM.from_pretrained(path)`` -- or ``from_pretrained`` above -- reads it."""
+        ``transformers.LlamaForCausalLM.from_pretrained(path)`` (``MistralForCausalLM`` / ``Qwen3ForCausalLM`` for those
+        model types; a config's own ``head_dim`` and Qwen3's q/k norm weights are written back) -- or ``from_pretrained``
+        above -- reads it."""
         import json
         import os
 
@@ -350,7 +395,7 @@ class LlamaForCausalLM(nn.Module):
         cfg = self.config
         self.model._quest_page_budget = token_budget // page_size
         self.model.iController = qutils.InferenceController(
-            cfg.num_hidden_layers, cfg.num_attention_heads, cfg.hidden_size // cfg.num_attention_heads, page_size,
+            cfg.num_hidden_layers, cfg.num_attention_heads, rope_mod.head_dim_of(cfg), page_size,
             self.model._quest_page_budget, max_seq_len, dtype, device, num_kv_heads=cfg.num_key_value_heads,
             layout=qutils.TensorLayout.parse(kv_layout))
         self._share_rope_table(device)
@@ -378,8 +423,8 @@ class LlamaForCausalLM(nn.Module):
     def capture_decode_graph(self, fused_layers: Optional[bool] = None) -> None:
         """Capture ONE decode step (all layers + lm_head) and keep it for ``decode_graph_step``.  ``fused_layers``
         (default: on for fp16 models unless ``QUEST_FUSED_LAYER=0``): the decoder layers' projections, norms, RoPE,
-        activation and residual adds run as 4 fused HIP launches per layer (csrc/decode_layer.hip) instead of ~14
-        rocBLAS / PyTorch launches.  Call after
+        activation and residual adds run as 4 fused HIP launches per layer (csrc/decode_layer.hip; 5 for a model with a
+        per-head q/k norm, ``forward_state_fused``) instead of ~14 rocBLAS / PyTorch launches.  Call after
         the prompt has been processed (any length: while the cache holds fewer pages than the budget the
         sparse layers attend all of them, like the reference's full-attention branch).  The
         graph reads its input from ``self.graph_input`` ``[1, 1, hidden]`` and leaves the logits in
@@ -461,7 +506,7 @@ class LlamaForCausalLM(nn.Module):
         cfg = self.config
         self.model._quest_page_budget = token_budget // page_size
         self.model.bController = qutils.BatchedInferenceController(
-            n_seqs, cfg.num_hidden_layers, cfg.num_attention_heads, cfg.hidden_size // cfg.num_attention_heads,
+            n_seqs, cfg.num_hidden_layers, cfg.num_attention_heads, rope_mod.head_dim_of(cfg),
             page_size, self.model._quest_page_budget, max_seq_len, dtype, device,
             num_kv_heads=cfg.num_key_value_heads, layout=qutils.TensorLayout.parse(kv_layout))
         self._share_rope_table(device)

@@ -1,7 +1,12 @@
 """Rotary-embedding parameters of a Llama config: which form the kernels take and, for the scaled types, the frequency
 table.
 
-Default and linear RoPE run the kernels' in-kernel formula ``(1 / rope_scale) * rope_theta^(-2i / D)``.  The ``llama3``
+Default and linear RoPE run the kernels' in-kernel formula ``(1 / rope_scale) * rope_theta^(-2i / D)``; the model types
+added after Llama (``mistral``, ``qwen3``: 32K-128K contexts with unscaled RoPE) take the table for default RoPE too --
+the formula's exp2f frequency differs from transformers' ``1 / theta^(2i / D)`` by up to 8e-7 relative and by an fp32 ulp
+of the highest frequencies, which times the position is an angle error of up to 0.008 rad at 131071 (2.4e-4 at 4096),
+where the table's angle equals transformers' bit for bit.  (Llama configs keep the formula for default RoPE, drift
+included: their behaviour is unchanged.)  The ``llama3``
 (Llama-3.1 / 3.2) and ``yarn`` (YaRN, e.g. NousResearch Yarn-Llama-2-7b-128k) scalings go through the kernels' table
 form: ``inv_freq`` (``D/2`` fp32) and ``attention_factor``, computed here with the fp32 torch expressions of Hugging
 Face's ``modeling_rope_utils`` (``_compute_llama3_parameters`` / ``_compute_yarn_parameters``), so that the frequencies
@@ -41,15 +46,29 @@ def rope_type(scaling: Optional[dict]) -> str:
     return kind
 
 
+def head_dim_of(config) -> int:
+    """The head dimension of a config: its ``head_dim`` field where it has one that is set (Qwen3, Mistral-Nemo: not
+    ``hidden_size / num_attention_heads``), else ``hidden_size // num_attention_heads``."""
+    return int(getattr(config, "head_dim", None) or config.hidden_size // config.num_attention_heads)
+
+
+def takes_table(config) -> bool:
+    """Whether the config's RoPE runs through the kernels' frequency-table form (else: the in-kernel formula)."""
+    kind = rope_type(getattr(config, "rope_scaling", None))
+    return kind in TABLE_TYPES or (kind == "default" and getattr(config, "model_type", "llama") != "llama")
+
+
 def rope_parameters(config) -> Optional[Tuple[torch.Tensor, float]]:
     """``(inv_freq, attention_factor)`` of a config whose RoPE takes the kernels' table form (``inv_freq``: CPU fp32
-    ``[D/2]``, D = hidden_size / num_attention_heads), ``None`` for default and linear RoPE (the in-kernel formula)."""
+    ``[D/2]``, D = ``head_dim_of(config)``), ``None`` where the in-kernel formula runs (``takes_table``: linear RoPE, and default RoPE of Llama configs)."""
     scaling = getattr(config, "rope_scaling", None)
     kind = rope_type(scaling)
-    if kind not in TABLE_TYPES:
+    if not takes_table(config):
         return None
     base = float(getattr(config, "rope_theta", 1e4))
-    dim = config.hidden_size // config.num_attention_heads
+    dim = head_dim_of(config)
+    if kind == "default":  # modeling_rope_utils' default: the unscaled frequencies, as transformers computes them
+        return 1.0 / (base ** (torch.arange(0, dim, 2, dtype=torch.int64, device="cpu").to(dtype=torch.float) / dim)), 1.0
     if kind == "llama3":
         return _llama3(scaling, base, dim), 1.0
     orig = scaling.get("original_max_position_embeddings") or config.max_position_embeddings

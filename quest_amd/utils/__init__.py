@@ -28,6 +28,7 @@ __all__ = [
     "decode_sparse_attn",
     "rms_norm_forward",
     "apply_rope_in_place",
+    "apply_qk_norm_rope_in_place",
     # extensions (fused launches; same results as the op pairs they replace)
     "decode_append_estimate",
     "decode_topk_sparse_attn",
@@ -63,6 +64,22 @@ def apply_rope_in_place(q: torch.Tensor, k: torch.Tensor, past_kv_len: int, rope
         return
     scale, theta = _rope_defaults(rope_scale, rope_theta)
     _kernels.apply_rope_in_place(q, k, past_kv_len, scale, theta)
+
+
+def apply_qk_norm_rope_in_place(q: torch.Tensor, k: torch.Tensor, past_kv_len: int, q_weight: torch.Tensor,
+                                k_weight: torch.Tensor, eps: float, rope_scale: Optional[float] = None,
+                                rope_theta: Optional[float] = None,
+                                rope_freqs: Optional[Tuple[torch.Tensor, float]] = None,
+                                states: Optional[torch.Tensor] = None) -> None:
+    """``apply_rope_in_place`` preceded by the per-head RMSNorm of q and k (weights ``[D]``, shared by the heads: Qwen3's
+    ``q_norm`` / ``k_norm``), both in ONE launch, in place (EXTENSION): fp32 from the loaded row to the single rounding.
+    ``states``: None = row i at ``past_kv_len + i``; else the step state(s) ``[N, 8]`` int32 of a controller
+    (``controller.step_states``) and row i = the decode token of sequence i at ``states[i].seq_len - 1`` (``past_kv_len``
+    unused): the state-driven form a captured step replays."""
+    scale, theta = _rope_defaults(rope_scale, rope_theta)
+    inv_freq, attn = rope_freqs if rope_freqs is not None else (None, 1.0)
+    _kernels.apply_qk_norm_rope_in_place(q, k, q_weight, k_weight, eps, past_kv_len=past_kv_len, rope_scale=scale,
+                                         rope_theta=theta, inv_freq=inv_freq, attention_factor=attn, states=states)
 
 
 def rms_norm_forward(input: torch.Tensor, weight: torch.Tensor, epsilon: float) -> torch.Tensor:
@@ -210,7 +227,12 @@ def _need_state(controller) -> None:
 # ``kv_tables``, ``meta_tables``, ``kv_layer``: controller.py), so the ``*_dyn`` and ``*_batched`` names below reach the
 # same launches.
 
-def _rope_at_state(q, k, rope_scale, rope_theta, rope_freqs, states) -> None:
+def _rope_at_state(q, k, rope_scale, rope_theta, rope_freqs, states, qk_norm=None) -> None:
+    """RoPE of every sequence's decode token at its state's position; ``qk_norm`` = ``(q_weight, k_weight, eps)``: the
+    per-head q/k RMSNorm + RoPE launch instead of the plain RoPE launch."""
+    if qk_norm is not None:
+        apply_qk_norm_rope_in_place(q, k, 0, qk_norm[0], qk_norm[1], qk_norm[2], rope_scale, rope_theta, rope_freqs, states)
+        return
     if rope_freqs is not None:
         _kernels.apply_rope_in_place_freqs(q, k, rope_freqs[0], rope_freqs[1], states=states)
         return
@@ -224,7 +246,7 @@ def _step_advance(ctl) -> None:
 
 
 def _decode_layer(q, k, v, ctl, layer_idx, scores, rope_scale, rope_theta, apply_rope, rope_freqs, tiles, out=None,
-                  one_launch=None, write_scores=False, advance_after=False) -> torch.Tensor:
+                  one_launch=None, write_scores=False, advance_after=False, qk_norm=None) -> torch.Tensor:
     """[RoPE] -> append+estimate -> top-k+attention (+merge) for every sequence of ``ctl``, the optional one-launch form
     first: ``decode_layer_dyn`` / ``decode_layer_batched`` describe the arguments."""
     _need_state(ctl)
@@ -232,7 +254,7 @@ def _decode_layer(q, k, v, ctl, layer_idx, scores, rope_scale, rope_theta, apply
     if advance_after:
         handler.arm_step_advance(ctl.step_states, ctl.kv_tables, ctl.meta_tables, ctl.page_size)
     if apply_rope:
-        _rope_at_state(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_states)
+        _rope_at_state(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_states, qk_norm)
     max_n = ctl.max_pages - 1
     kvb, mb = ctl.kv_layer(layer_idx), ctl.metadata_layer(layer_idx)
     o = torch.empty_like(q) if out is None else out
@@ -261,12 +283,12 @@ def _decode_layer(q, k, v, ctl, layer_idx, scores, rope_scale, rope_theta, apply
 
 
 def _decode_layer_dense(q, k, v, ctl, layer_idx, rope_scale, rope_theta, apply_rope, rope_freqs, fuse_append, out=None,
-                        advance_after=False) -> torch.Tensor:
+                        advance_after=False, qk_norm=None) -> torch.Tensor:
     """[RoPE] -> append + attention over all pages (+merge) for every sequence of ``ctl``: ``decode_layer_dense_dyn``."""
     _need_state(ctl)
     handler = ctl._dense_handler
     if apply_rope:
-        _rope_at_state(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_states)
+        _rope_at_state(q, k, rope_scale, rope_theta, rope_freqs, ctl.step_states, qk_norm)
     o = torch.empty_like(q) if out is None else out
     kvb, mb = ctl.kv_layer(layer_idx), ctl.metadata_layer(layer_idx)
     if advance_after:
@@ -287,7 +309,7 @@ def decode_layer_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iControl
                      layer_idx: int, scores: torch.Tensor, rope_scale: Optional[float] = None,
                      rope_theta: Optional[float] = None, apply_rope: bool = False,
                      tiles: Optional[bool] = None, advance_after: bool = False,
-                     rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
+                     rope_freqs: Optional[Tuple[torch.Tensor, float]] = None, qk_norm=None) -> torch.Tensor:
     """One layer of a decode token in the sparse regime (pages > budget), every length read from the
     device-resident state: [RoPE] -> append+estimate -> top-k+attention (+merge).  ``scores`` is a
     caller-owned ``[Hq, >= max_pages]`` fp16 scratch (``score_scratch``).  ``tiles``: None = the tiles launches for pools
@@ -295,21 +317,23 @@ def decode_layer_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iControl
     ``advance_after``: the LAST layer of a step -- the next token's reservation (``step_advance_dyn``) rides in this layer's
     merge launch instead of heading the next step as a launch of its own (the first token is reserved by one
     ``step_advance_dyn`` before the first step; the host mirror ``prepare_metadata(1)`` follows every step as before).
-    ``rope_freqs``: the frequency-table RoPE of ``apply_rope_in_place`` (llama3 / yarn configs)."""
+    ``rope_freqs``: the frequency-table RoPE of ``apply_rope_in_place`` (llama3 / yarn configs).
+    ``qk_norm``: ``(q_weight, k_weight, eps)`` with ``apply_rope=True`` -- the per-head q/k RMSNorm + RoPE launch
+    (``apply_qk_norm_rope_in_place``) takes the place of the RoPE launch."""
     return _decode_layer(q, k, v, iController, layer_idx, scores, rope_scale, rope_theta, apply_rope, rope_freqs, tiles,
-                         advance_after=advance_after)
+                         advance_after=advance_after, qk_norm=qk_norm)
 
 
 def decode_layer_dense_dyn(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, iController: InferenceController,
                            layer_idx: int, rope_scale: Optional[float] = None, rope_theta: Optional[float] = None,
                            apply_rope: bool = False, fuse_append: bool = True, advance_after: bool = False,
-                           rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
+                           rope_freqs: Optional[Tuple[torch.Tensor, float]] = None, qk_norm=None) -> torch.Tensor:
     """One FULL-KV layer of a decode token (``advance_after``: see ``decode_layer_dyn``), every length read from the device-resident state:
     [RoPE] -> append + attention over all pages in ONE launch (group-shared kernel; the workgroup that attends the
     current page takes the new token from k / v, writes it to the pool and folds it into the metadata) (+merge).  Shapes
     outside the group-shared kernel take the separate append launch.  Needs ``begin_graph_decode(dense_layers=True)``."""
     return _decode_layer_dense(q, k, v, iController, layer_idx, rope_scale, rope_theta, apply_rope, rope_freqs, fuse_append,
-                               advance_after=advance_after)
+                               advance_after=advance_after, qk_norm=qk_norm)
 
 
 def step_advance_batched(bController: BatchedInferenceController) -> None:
@@ -321,7 +345,7 @@ def decode_layer_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bCon
                          rope_theta: Optional[float] = None, apply_rope: bool = False,
                          out: Optional[torch.Tensor] = None, one_launch: Optional[bool] = None,
                          write_scores: bool = False, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None,
-                         tiles: Optional[bool] = None) -> torch.Tensor:
+                         tiles: Optional[bool] = None, qk_norm=None) -> torch.Tensor:
     """``decode_layer_dyn`` for every sequence at once; ``scores`` is ``[n_seqs, Hq, >= max_pages]`` fp16.
 
     ``tiles`` (two-launch form): None = the tiles launches for pools of at least ``bController.tiles_min_pages`` pages per
@@ -342,17 +366,18 @@ def decode_layer_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, bCon
     the scratch after this call must pass ``write_scores=True`` or ``one_launch=False``.  Which form ran is left in
     ``bController.last_layer_launches`` (1 or 2)."""
     return _decode_layer(q, k, v, bController, layer_idx, scores, rope_scale, rope_theta, apply_rope, rope_freqs, tiles,
-                         out=out, one_launch=one_launch, write_scores=write_scores)
+                         out=out, one_launch=one_launch, write_scores=write_scores, qk_norm=qk_norm)
 
 
 def decode_layer_dense_batched(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor,
                                bController: BatchedInferenceController, layer_idx: int,
                                rope_scale: Optional[float] = None, rope_theta: Optional[float] = None,
                                apply_rope: bool = False, out: Optional[torch.Tensor] = None,
-                               fuse_append: bool = True, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None) -> torch.Tensor:
+                               fuse_append: bool = True, rope_freqs: Optional[Tuple[torch.Tensor, float]] = None,
+                               qk_norm=None) -> torch.Tensor:
     """``decode_layer_dense_dyn`` for every sequence at once (needs ``begin_graph_decode(dense_layers=True)``)."""
     return _decode_layer_dense(q, k, v, bController, layer_idx, rope_scale, rope_theta, apply_rope, rope_freqs, fuse_append,
-                               out=out)
+                               out=out, qk_norm=qk_norm)
 
 
 # ---- the reference's four operators of a decode step, one by one, for a whole batch (eager: no captured graph needed;

@@ -10,6 +10,9 @@ lm_head -- is captured in a hipGraph and replayed.  First `skip` = 2 layers run 
 (quest/models/llama.py:428-439).
 
     python scripts/bench_textgen.py --ctx 32768 --token-budget 2048
+    # Qwen3-8B shapes (per-head q/k norm, head_dim its own field); QUEST_FUSED_LAYER=0 takes the module path
+    python scripts/bench_textgen.py --family qwen3 --layers 36 --heads 32 --kv-heads 8 --head-dim 128 --inter 12288 \
+        --vocab 151936 --generate 64 [--seqs 8]
 """
 import argparse
 import json
@@ -61,7 +64,7 @@ def time_batched(cfg, a, dense, dev):
         model.model._quest_skip_layer = a.layers
     b = model.model.bController
     g = torch.Generator(device=dev).manual_seed(1)
-    D = a.hidden // a.heads
+    D = a.head_dim
     k = torch.empty(a.ctx, a.kv_heads, D, dtype=torch.float16, device=dev)
     v = torch.empty_like(k)
     for c in b.seqs:
@@ -124,6 +127,10 @@ def main():
     ap.add_argument("--rope", choices=["default", "llama3"], default="default",
                     help="RoPE of the random-weight model: default (theta 1e4, the in-kernel formula) or Llama-3.1's "
                          "llama3 scaling (theta 5e5, factor 8: the kernels' frequency-table form)")
+    ap.add_argument("--family", choices=["llama", "mistral", "qwen3"], default="llama",
+                    help="model family of the random-weight model: mistral = Llama arithmetic, qwen3 = per-head q/k RMSNorm "
+                         "before RoPE; both run their default RoPE through the frequency table (theta 1e6)")
+    ap.add_argument("--head-dim", type=int, default=None, help="head dimension (default: hidden / heads)")
     a = ap.parse_args()
     from quest_amd.models.llama import LlamaConfig, LlamaForCausalLM
     import quest_amd.utils as qu
@@ -131,7 +138,10 @@ def main():
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     cfg = LlamaConfig(vocab_size=a.vocab, hidden_size=a.hidden, intermediate_size=a.inter, num_hidden_layers=a.layers,
-                      num_attention_heads=a.heads, num_key_value_heads=a.kv_heads, max_position_embeddings=a.ctx + 1024)
+                      num_attention_heads=a.heads, num_key_value_heads=a.kv_heads, max_position_embeddings=a.ctx + 1024,
+                      head_dim=a.head_dim, qk_norm=a.family == "qwen3", model_type=a.family,
+                      rope_theta=1e4 if a.family == "llama" else 1e6)
+    a.head_dim = a.head_dim or a.hidden // a.heads
     if a.rope == "llama3":
         cfg.rope_scaling = {"rope_type": "llama3", "factor": 8.0, "low_freq_factor": 1.0, "high_freq_factor": 4.0,
                             "original_max_position_embeddings": 8192}
@@ -157,6 +167,7 @@ def main():
             cfg = LlamaConfig.from_hf_dict(json.load(f))
         a.layers, a.hidden, a.heads, a.kv_heads = (cfg.num_hidden_layers, cfg.hidden_size, cfg.num_attention_heads,
                                                    cfg.num_key_value_heads)
+        a.head_dim, a.family = cfg.head_dim or a.hidden // a.heads, cfg.model_type
         ckpt_info = dict(ckpt_info or {}, path=a.checkpoint,
                          files=sorted(f for f in os.listdir(a.checkpoint) if f.endswith((".safetensors", ".json"))),
                          bytes=sum(os.path.getsize(os.path.join(a.checkpoint, f)) for f in os.listdir(a.checkpoint)))
@@ -166,6 +177,7 @@ def main():
         print(json.dumps({"bench": "e2e batched decode, random-weight Llama", "sequences": a.seqs, "ctx": a.ctx, "kv_layout": a.layout,
                           "token_budget": a.token_budget, "layers": a.layers, "hidden": a.hidden, "heads": a.heads,
                           "kv_heads": a.kv_heads, "intermediate": a.inter, "vocab": a.vocab, "dense_first_layers": 2,
+                          "family": a.family, "head_dim": a.head_dim,
                           "fused_decoder_layer_launches": getattr(time_batched, "fused_layers", None), "ms_per_step_quest": q_ms,
                           "ms_per_step_full_kv": d_ms, "tokens_per_s_quest": a.seqs / (q_ms * 1e-3),
                           "tokens_per_s_full_kv": a.seqs / (d_ms * 1e-3), "speedup": d_ms / q_ms}))
@@ -190,7 +202,7 @@ def main():
         model.quest_init(16, a.ctx + 256 + a.generate, budget, kv_layout=a.layout)
         ctl = model.model.iController
         g = torch.Generator(device=dev).manual_seed(1)
-        D = a.hidden // a.heads
+        D = a.head_dim
         if a.real_prefill:
             import time
             x = torch.randn(1, a.ctx, a.hidden, generator=g, device=dev, dtype=torch.float16)
@@ -221,6 +233,7 @@ def main():
             # greedy generation by one graph replay per token (device-resident lengths; the host only feeds the token)
             import time
             model.capture_decode_graph()
+            gen_fused = bool(model.fused_layers)
             tok = torch.zeros(1, 1, dtype=torch.long, device=dev)
             with torch.inference_mode():
                 for _ in range(3):
@@ -235,12 +248,13 @@ def main():
         torch.cuda.empty_cache()
     out = {"bench": "e2e decode latency, random-weight Llama", "ctx": a.ctx, "token_budget": a.token_budget,
            "page_budget_pages": a.token_budget // 16, "layers": a.layers, "hidden": a.hidden, "heads": a.heads,
-           "kv_heads": a.kv_heads, "dense_first_layers": 2, "kv_layout": a.layout, "rope": a.rope,
+           "kv_heads": a.kv_heads, "dense_first_layers": 2, "kv_layout": a.layout, "rope": a.rope, "family": a.family,
+           "head_dim": a.head_dim, "intermediate": a.inter, "vocab": a.vocab,
            "ms_per_token_quest": results["quest"], "ms_per_token_full_kv": results["dense"],
            "speedup": results["dense"] / results["quest"],
            "reference_published": "RTX 6000 Ada, ctx 32768 FP16: 36.8 ms -> 21.2 ms @ budget 2048 (1.74x)"}
     if gen_ms:
-        out["generation_fused_decoder_layers"] = os.environ.get("QUEST_FUSED_LAYER", "1") != "0"
+        out["generation_fused_decoder_layers"] = gen_fused
         out["generated_tokens"] = a.generate
         out["ms_per_generated_token_quest"] = gen_ms["quest"]
         out["ms_per_generated_token_full_kv"] = gen_ms["dense"]

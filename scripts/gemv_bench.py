@@ -4,7 +4,10 @@ Cache, hipGraph + HIP events).  QUEST_GEMV_CFG="RW,U" forces a workgroup shape. 
 With --tokens N (2..16): the N-token launches (csrc/decode_layer.hip skinny_kernel; QUEST_SKINNY_CFG="NW,U") next to
 torch.nn.functional.linear on the same [N, in] inputs (hipBLASLt).
 With --rope-ab: the q/k/v+RoPE launch at Llama-3.1-8B shapes (hidden 4096, 32 / 8 heads, head_dim 128), batch 1 and 8
-tokens, RoPE formula (rope_scale / rope_theta) vs the llama3 frequency table, alternating A B A B."""
+tokens, RoPE formula (rope_scale / rope_theta) vs the llama3 frequency table, alternating A B A B.
+With --qk-norm-ab: Qwen3-8B shapes (hidden 4096, 32 / 8 heads of 128), batch 1 and 8 tokens: the rotating q/k/v launch
+(frequency table) beside the unrotated one (quest_decode_qkv*) and the per-head q/k norm + RoPE launch that follows it,
+alternating A B A B."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -83,3 +86,41 @@ if "--rope-ab" in sys.argv:
     for key, ts in times.items():
         print(f"qkv+rope Llama-3.1-8B {key[0]:8s} {key[1]:7s}: " + " ".join(f"{t:6.2f}" for t in ts)
               + f"  us (median {sorted(ts)[len(ts) // 2]:6.2f}, 48 MiB: {48 * 1.048576 / sorted(ts)[len(ts) // 2]:5.2f} TB/s)")
+
+if "--qk-norm-ab" in sys.argv:
+    from quest_amd.models import rope as qrope
+    from types import SimpleNamespace
+    cfgq = SimpleNamespace(hidden_size=4096, num_attention_heads=32, head_dim=128, max_position_embeddings=40960,
+                           rope_theta=1e6, rope_scaling=None, model_type="qwen3")
+    inv_freq, factor = qrope.device_rope_parameters(cfgq, dev)
+    wk8, wv8 = w(1024, H), w(1024, H)
+    qn = (1 + 0.1 * torch.randn(128, generator=g, device=dev)).half()
+    kn = (1 + 0.1 * torch.randn(128, generator=g, device=dev)).half()
+    k8 = torch.empty(1, 8, 128, device=dev, dtype=torch.float16); v8 = torch.empty_like(k8)
+    X8 = torch.randn(8, H, generator=g, device=dev, dtype=torch.float16)
+    Q8 = torch.empty(8, 32, 128, device=dev, dtype=torch.float16); K8 = torch.empty(8, 8, 128, device=dev, dtype=torch.float16)
+    V8 = torch.empty_like(K8)
+    ST8 = torch.tensor([[32768 + 17 * i, 1, 1, 0, 1, 1, 0, 0] for i in range(8)], dtype=torch.int32, device=dev)
+    st1 = torch.tensor([[32768, 1, 1, 0, 1, 1, 0, 0]], dtype=torch.int32, device=dev)
+    # the norm + RoPE launch rewrites q / k in place: the values wander, the time does not depend on them
+    launches = {
+        ("batch 1", "q/k/v + RoPE (table)"): lambda i: _kernels.decode_qkv_rope_freqs(x, gamma, 1e-6, wq[i], wk8[i], wv8[i], q, k8, v8,
+                                                                                     128, inv_freq, factor, st1),
+        ("batch 1", "q/k/v unrotated"): lambda i: _kernels.decode_qkv(x, gamma, 1e-6, wq[i], wk8[i], wv8[i], q, k8, v8),
+        ("batch 1", "q/k norm + RoPE"): lambda i: _kernels.apply_qk_norm_rope_in_place(q, k8, qn, kn, 1e-6, inv_freq=inv_freq,
+                                                                                      attention_factor=factor, states=st1),
+        ("batch 1", "RoPE alone"): lambda i: _kernels.apply_rope_in_place_freqs(q, k8, inv_freq, factor, states=st1),
+        ("8 tokens", "q/k/v + RoPE (table)"): lambda i: _kernels.decode_qkv_rope_batched_freqs(X8, gamma, 1e-6, wq[i], wk8[i], wv8[i],
+                                                                                              Q8, K8, V8, 128, inv_freq, factor, ST8),
+        ("8 tokens", "q/k/v unrotated"): lambda i: _kernels.decode_qkv_batched(X8, gamma, 1e-6, wq[i], wk8[i], wv8[i], Q8, K8, V8),
+        ("8 tokens", "q/k norm + RoPE"): lambda i: _kernels.apply_qk_norm_rope_in_place(Q8, K8, qn, kn, 1e-6, inv_freq=inv_freq,
+                                                                                       attention_factor=factor, states=ST8),
+        ("8 tokens", "RoPE alone"): lambda i: _kernels.apply_rope_in_place_freqs(Q8, K8, inv_freq, factor, states=ST8),
+    }
+    times = {key: [] for key in launches}
+    for _ in range(4):  # A B A B
+        for key, fn in launches.items():
+            times[key].append(graph_time(fn, NSET, 20))
+    for key, ts in times.items():
+        print(f"Qwen3-8B {key[0]:8s} {key[1]:22s}: " + " ".join(f"{t:6.2f}" for t in ts)
+              + f"  us (median {sorted(ts)[len(ts) // 2]:6.2f})")

@@ -54,7 +54,7 @@ void rms_norm_forward(torch::Tensor input, torch::Tensor weight, torch::Tensor o
 // bsk_ops.h:34-39
 void topk_filtering(torch::Tensor estimated_value, torch::Tensor estimated_indices, torch::Tensor d_out,
                     torch::Tensor indices_out, torch::Tensor buf, unsigned int page_budget) {
-    int rc = quest_topk_filtering(estimated_value.data_ptr(), static_cast<const int32_t*>(estimated_indices.data_ptr()),
+    int rc = quest_topk_filtering(estimated_value.data_ptr(), 0, static_cast<const int32_t*>(estimated_indices.data_ptr()),
                                   d_out.data_ptr(), static_cast<int32_t*>(indices_out.data_ptr()), buf.data_ptr(),
                                   estimated_value.size(0), estimated_value.size(1), page_budget, stream());
     TORCH_CHECK(rc == 0, "topk_filtering failed with error code ", quest_error_string(rc));

@@ -17,14 +17,16 @@
  *     fp16): q, k, v, o and the score rows of that call have that type.  An unknown value, or two views of one call with
  *     different values, is QUEST_EINVAL before anything is launched.  A decode handler has a type of its own
  *     (quest_decode_set_dtype, default fp16) and refuses views of the other one with QUEST_EINVAL.  The two operators
- *     that take neither a view nor a handler have one typed entry each: quest_apply_rope_in_place_dtype (all four RoPE
- *     forms) and quest_rms_norm_forward_dtype; every other symbol keeps its signature and, given zeroed views, its fp16
- *     meaning.  Top-k (quest_topk_filtering*) orders 16-bit sign-magnitude bit patterns and is the same code for both.
+ *     that take neither a view nor a handler have one typed entry each: quest_apply_rope_in_place_dtype (every RoPE
+ *     form) and quest_rms_norm_forward_dtype; every other symbol means fp16 when given zeroed views.  Top-k (quest_topk_filtering*) orders 16-bit sign-magnitude bit patterns and is the same code for both.
  *     bf16 differences: metadata max / min treat patterns above 0x7f80 as NaN, a new page's entry starts from -/+ the
  *     largest finite bf16 (0xff7f / 0x7f7f) instead of -/+65504, scores are bf16_rne of the same fp32 sum, partial
  *     attention states stay fp32.  fp16 only: the decode-layer projections (quest_decode_norm_gemv, _gemv_residual,
- *     _mlp_gate_up, _qkv_rope*, _qkv*) and quest_decode_layer_fused_batched, which returns QUEST_EUNSUPPORTED for bf16 views
+ *     _mlp_gate_up, _qkv_rope, _qkv and their _batched forms) and quest_decode_layer_fused_batched, which returns QUEST_EUNSUPPORTED for bf16 views
  *     (the caller issues quest_append_estimate_batched + quest_decode_forward_fused_topk_batched).
+ *   - One entry per operator.  An operator that reads lengths and last pages from device-resident step state
+ *     (quest_step_state_t) has the suffix _batched and takes a quest_batch_t; one sequence is the batch of one.  Row strides
+ *     and tile offsets are arguments of the one entry, 0 = contiguous rows / whole rows.
  *   - Return value: 0 on success; a positive value is a hipError_t from a launch; a negative
  *     value is one of the QUEST_E* argument errors below.  quest_error_string() names both.
  *     Nothing throws; nothing allocates except quest_decode_begin_forward (workspace, like
@@ -138,14 +140,11 @@ int quest_estimate_attn_score(const void* q, void* o, uint32_t num_qo_heads, uin
  * the cache + folds it into its page's metadata, and scores all pages but the current one.  The two
  * halves touch disjoint bytes (the estimate excludes the current page's entry), so the result is
  * identical to calling quest_append_kv_cache_decode then quest_estimate_attn_score.
+ * o_stride: elements between the rows of consecutive query heads (0 = n_out, contiguous rows).
  */
 int quest_append_estimate(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                          uint32_t num_qo_heads, uint32_t n_out, quest_paged_kv_t metadata,
+                          uint32_t num_qo_heads, uint32_t n_out, uint32_t o_stride, quest_paged_kv_t metadata,
                           quest_stream_t stream);
-/* The same with a row stride for `o` (elements between the rows of consecutive query heads; 0 = n_out). */
-int quest_append_estimate_strided(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                  uint32_t num_qo_heads, uint32_t n_out, uint32_t o_stride, quest_paged_kv_t metadata,
-                                  quest_stream_t stream);
 
 /*
  * topk_filtering (bsk_ops.h:34-39, topk.cu:7-46 -> decode_select_k, decode_select_k.cuh:25-62,
@@ -153,16 +152,12 @@ int quest_append_estimate_strided(const void* k, const void* v, quest_paged_kv_t
  * estimated_value/indices: [num_heads][num_pages]; d_out/indices_out: [num_heads][page_budget].
  * Deterministic: ties at the k-th value go to the lowest column; output in ascending column order.
  * `buf` is the reference's scratch argument; unused (may be NULL).
+ * value_stride: elements between consecutive heads' rows of `estimated_value` (0 = num_pages, contiguous rows): serves the
+ * padded score rows quest_append_estimate writes without a compacting copy.
  */
-int quest_topk_filtering(const void* estimated_value, const int32_t* estimated_indices, void* d_out,
-                         int32_t* indices_out, void* buf, uint32_t num_heads, uint32_t num_pages,
-                         uint32_t page_budget, quest_stream_t stream);
-
-/* The same with a row stride for `estimated_value` (elements between consecutive heads' rows; 0 = num_pages): serves the
- * padded score rows quest_append_estimate_strided writes without a compacting copy. */
-int quest_topk_filtering_strided(const void* estimated_value, uint32_t value_stride, const int32_t* estimated_indices,
-                                 void* d_out, int32_t* indices_out, void* buf, uint32_t num_heads, uint32_t num_pages,
-                                 uint32_t page_budget, quest_stream_t stream);
+int quest_topk_filtering(const void* estimated_value, uint32_t value_stride, const int32_t* estimated_indices, void* d_out,
+                         int32_t* indices_out, void* buf, uint32_t num_heads, uint32_t num_pages, uint32_t page_budget,
+                         quest_stream_t stream);
 
 /*
  * BatchDecodeWithPagedKVCachePyTorchWrapper (bsk_ops.h:88-117, approx_attn.cu:27-150 ->
@@ -206,28 +201,24 @@ int quest_decode_forward_shared(quest_decode_handler_t* h, const void* q, void* 
  *   page_table  paged_kv.indices = the sequence's page table [n_scores + 1] (kv_indices_with_last)
  *   topk_val_out / topk_idx_out  optional [num_qo_heads][n_selected_pages]: the selection, bit-identical
  *                to quest_topk_filtering's outputs (same routine), for callers that inspect it.
+ *   score_stride  elements between the rows of `scores` (0 = n_scores).  The reference's score tensor is a contiguous
+ *                [num_qo_heads][pages - 1] (quest/utils/__init__.py:171-205), whose rows are only 2-byte aligned; rows padded
+ *                to a multiple of 8 columns (16 bytes: quest_append_estimate writes them) let the front end fetch a thread's
+ *                scores with one vector load.  Both layouts are served in ONE launch (also the reference's layout beyond 4096
+ *                pages: every workgroup reads the 8-byte aligned stream below its row and skips the 0-3 leading columns of
+ *                the previous row; up to QUEST_TOPK_MAX_ROW - 3 pages -- QUEST_EUNSUPPORTED beyond: callers then issue
+ *                quest_topk_filtering + quest_decode_forward).
  */
 int quest_decode_forward_fused_topk(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,
-                                    uint32_t num_qo_heads, const void* scores, uint32_t n_scores,
+                                    uint32_t num_qo_heads, const void* scores, uint32_t n_scores, uint32_t score_stride,
                                     void* topk_val_out, int32_t* topk_idx_out, float* lse, quest_stream_t stream);
-/* The same with a row stride for `scores` (elements; 0 = n_scores).  The reference's score tensor is a contiguous
- * [num_qo_heads][pages - 1] (quest/utils/__init__.py:171-205), whose rows are only 2-byte aligned; rows padded to a
- * multiple of 8 columns (16 bytes: quest_append_estimate_strided writes them) let the front end fetch a thread's
- * scores with one vector load.  Both layouts are served in ONE launch (since round 5 also the reference's layout beyond 4096
- * pages: every workgroup reads the 8-byte aligned stream below its row and skips the 0-3 leading columns of the previous
- * row; up to QUEST_TOPK_MAX_ROW - 3 pages -- QUEST_EUNSUPPORTED beyond: callers then issue quest_topk_filtering +
- * quest_decode_forward). */
-int quest_decode_forward_fused_topk_strided(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,
-                                            uint32_t num_qo_heads, const void* scores, uint32_t n_scores,
-                                            uint32_t score_stride, void* topk_val_out, int32_t* topk_idx_out, float* lse,
-                                            quest_stream_t stream);
 
 /*
  * Device-resident step state (host planning rewrite).  The reference rebuilds page-table
  * tensors and re-plans on the host for every token (quest/utils/controller.py:80-129); with the sequence
  * state in device memory a decode step captured ONCE in a hipGraph can be replayed token after token while
- * the sequence grows: quest_step_state_advance is prepare_metadata(1) on the device, and the *_dyn entry
- * points read lengths / last-page ids from the state instead of from their by-value arguments.
+ * the sequence grows: quest_step_state_advance_batched is prepare_metadata(1) on the device, and the STATE-DRIVEN entries
+ * (the *_batched ones below) read lengths / last-page ids from the state instead of from the by-value fields of their views.
  * The page tables must be materialised up to the pool capacity (page i of the sequence = kv_table[i]).
  */
 typedef struct quest_step_state {
@@ -238,92 +229,24 @@ typedef struct quest_step_state {
     int32_t n_meta_pages;
     int32_t meta_last_page_len;
     int32_t meta_last_page_idx;
-    int32_t reserved;           /* set to 1 by quest_step_state_advance when the pool is exhausted */
+    int32_t reserved;           /* set to 1 by quest_step_state_advance_batched when the pool is exhausted */
 } quest_step_state_t;
 
-/* Reserve room for one more token: the device-side prepare_metadata(1) (controller.py:72-76).  The tables
- * hold max_kv_pages / max_meta_pages entries (the pools' capacities); when the next token would not fit the
- * state is left unchanged and `reserved` is set, so a replayed graph can never index past a table. */
-int quest_step_state_advance(quest_step_state_t* state, const int32_t* kv_table, const int32_t* meta_table,
-                             uint32_t page_size, uint32_t max_kv_pages, uint32_t max_meta_pages,
-                             quest_stream_t stream);
-
-/* quest_append_estimate with lengths / last-page ids / n_out (= state->n_pages - 1) taken from `state`.
- * o is [num_qo_heads][o_stride] with o_stride >= max_n_out, the largest n_out the graph will ever see
- * (the grid is sized for it; surplus workgroups exit). */
-int quest_append_estimate_dyn(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                              uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
-                              quest_paged_kv_t metadata, const quest_step_state_t* state, quest_stream_t stream);
-
-/* quest_decode_forward_fused_topk with the row length (state->n_pages - 1) and the current page taken
- * from `state`; scores is [num_qo_heads][score_stride].  The plan (selected-page count) is the one of
- * begin_forward and must not exceed state->n_pages - 1 for the life of the graph. */
-int quest_decode_forward_fused_topk_dyn(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,
-                                        uint32_t num_qo_heads, const void* scores, uint32_t score_stride,
-                                        uint32_t max_n_scores, const quest_step_state_t* state, float* lse,
-                                        quest_stream_t stream);
-
 /*
- * The same pair for LONG score rows (round 5; cfg 4: 8191 pages), with TILE MAXIMA handed across the kernel boundary: the
- * estimate workgroup that holds the scores of 8 consecutive pages also stores the largest of them (as an order-preserving
- * 16-bit key) at o[h][tile_max_offset + page / 8], and the attention launch selects in two short passes -- the top-k TILES by
- * maximum (a sufficient candidate set under the declared tie rule: csrc/decode_device.cuh sparse_decode_tiles_body), then the
- * exact top-k over those tiles' 8 k scores -- instead of passes over the whole row in every workgroup of a head.  Same
- * selection, same outputs as quest_append_estimate_dyn + quest_decode_forward_fused_topk_dyn.
- * tile_max_offset must be max_n rounded up to 8 columns; rows 16-byte aligned with
- * stride >= tile_max_offset + ceil(max_n / 8) rounded up to 4.  Plans with at most 256 selected pages, page_size 16, rows
- * up to 16384 pages; QUEST_EUNSUPPORTED otherwise.  The estimate side needs its workgroup tile to be a multiple of 8 pages
- * wide (head_dim 256: the tile covers 4 kv heads instead of 8); a shape for which no such tile exists returns
- * QUEST_EUNSUPPORTED before anything is launched, and the caller takes quest_append_estimate_dyn instead.
- */
-int quest_append_estimate_tiles_dyn(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                    uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out, uint32_t tile_max_offset,
-                                    quest_paged_kv_t metadata, const quest_step_state_t* state, quest_stream_t stream);
-int quest_decode_forward_fused_topk_tiles_dyn(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,
-                                              uint32_t num_qo_heads, const void* scores, uint32_t score_stride,
-                                              uint32_t max_n_scores, uint32_t tile_max_offset,
-                                              const quest_step_state_t* state, float* lse, quest_stream_t stream);
-
-/* quest_append_kv_cache_decode with lengths / last-page ids from `state` (dense layers of a replayed step). */
-int quest_append_kv_cache_decode_dyn(const void* k, const void* v, quest_paged_kv_t kv, quest_paged_kv_t metadata,
-                                     const quest_step_state_t* state, quest_stream_t stream);
-
-/* quest_decode_forward_shared over ALL pages of the sequence (state->n_pages - 1 listed pages + the current
- * one): paged_kv.indices = the full page table.  Plan with begin_forward(n_selected_pages = pool capacity - 1);
- * workgroups past the live length contribute empty partial states. */
-int quest_decode_forward_shared_dyn(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,
-                                    uint32_t num_qo_heads, const quest_step_state_t* state, float* lse,
-                                    quest_stream_t stream);
-
-/* quest_append_kv_cache_decode_dyn + quest_decode_forward_shared_dyn in ONE launch (round 4: a full-KV layer of a captured
- * step = attention + merge instead of append + attention + merge; the reference's pair of calls is QuestAttention.py:106
- * and :125-132 / page.cu:6-99).  k, v: the new token [1][kv heads][head_dim], not yet in the pool: the one workgroup per
- * kv head that attends the current page takes the row from k / v, writes it to the pool and folds k into the page's
- * (max, min) metadata entry -- same pool bytes as the separate append.  metadata: the layer's metadata pool (same
- * geometry as the KV pool; lengths from `state`).  QUEST_EUNSUPPORTED for shapes outside the group-shared kernel
- * (page_size 16, head_dim 64 / 128): issue the two launches then. */
-int quest_decode_append_forward_shared_dyn(quest_decode_handler_t* h, const void* k, const void* v,
-                                           quest_paged_kv_t metadata, const void* q, void* o, quest_paged_kv_t paged_kv,
-                                           uint32_t num_qo_heads, const quest_step_state_t* state, float* lse,
-                                           quest_stream_t stream);
-
-/* quest_apply_rope_in_place for one decode token with past_kv_len = state->seq_len - 1. */
-int quest_apply_rope_in_place_dyn(void* q, void* k, uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
-                                  float rope_scale, float rope_theta, const quest_step_state_t* state,
-                                  quest_stream_t stream);
-
-/*
- * Batched state-driven step (SURVEY.md 8f-3 second half: the reference fixes `constexpr batch_size = 1`,
+ * The sequences a state-driven launch serves (SURVEY.md 8f-3 second half: the reference fixes `constexpr batch_size = 1`,
  * approx_attn.cu:113 / estimate.cu:14; BASELINE config 5 decodes 8 sequences per GPU).  One launch serves
  * n_seqs independent sequences (grid.z / grid.y = sequence), no data is shared between them:
  *   - ONE KV pool and ONE metadata pool hold every sequence's pages (`data` of the views below);
  *   - page tables are rows of one int32 matrix: sequence i's table = indices + i * *_table_stride,
- *     materialised up to its capacity like the single-sequence tables above;
+ *     each materialised up to its capacity;
  *   - `state` is an array of n_seqs step states; q / o / k / v are [n_seqs][heads][dim], scores
  *     [n_seqs][num_qo_heads][score_stride], lse [n_seqs][num_qo_heads].
- * Per sequence: pools, estimates and page selections are bit-identical to the single-sequence *_dyn entry
- * points; attention outputs too when the work split (pages per workgroup) is the same, otherwise they differ
- * by the fp32 rounding of a different partial-state merge order (tests: <= 2e-3).
+ * A SINGLE SEQUENCE is the batch {1, 0, 0, 0, NULL}: its tables are plain arrays, and with n_seqs == 1 no entry reads the
+ * strides -- except quest_step_state_advance_batched, which checks them against the capacities for every n_seqs (pass the
+ * capacities there).  It runs the same device code as sequence 0 of a larger batch.
+ * Per sequence, pools, estimates and page selections do not depend on n_seqs, bit for bit; attention outputs neither when
+ * the work split (pages per workgroup) is the same, otherwise they differ by the fp32 rounding of a different
+ * partial-state merge order (tests: <= 2e-3).
  */
 typedef struct quest_batch {
     uint32_t n_seqs;
@@ -338,64 +261,80 @@ typedef struct quest_batch {
     const int32_t* page_budgets;
 } quest_batch_t;
 
-/* quest_step_state_advance for every sequence of the batch (tables: [n_seqs][*_table_stride], each row
- * valid up to max_kv_pages / max_meta_pages entries). */
+/* Reserve room for one more token of every sequence: the device-side prepare_metadata(1) (controller.py:72-76).  The tables
+ * ([n_seqs][*_table_stride]) hold max_kv_pages / max_meta_pages valid entries per row (the pools' capacities); when the
+ * next token would not fit the state is left unchanged and `reserved` is set, so a replayed graph can never index past a
+ * table. */
 int quest_step_state_advance_batched(quest_step_state_t* state, const int32_t* kv_tables, const int32_t* meta_tables,
                                      uint32_t page_size, uint32_t max_kv_pages, uint32_t max_meta_pages,
                                      quest_batch_t batch, quest_stream_t stream);
 
-/* The same reservation RIDING IN A STEP'S LAST LAUNCH (round 6): quest_step_state_advance at the head of a captured step is a
- * 1-thread launch of dependent loads -- 4.7 us per token.  Nothing after a layer's merge launch reads the step state, so the
+/* The same reservation RIDING IN A STEP'S LAST LAUNCH (round 6): quest_step_state_advance_batched at the head of a captured
+ * step is a 1-thread launch of dependent loads -- 4.7 us per token.  Nothing after a layer's merge launch reads the step state, so the
  * reservation for the NEXT token can be made there: arm it on the handler right before the last layer's forward call of a
  * step; the merge launch of that call carries it (one thread per sequence of its first workgroup) and the handler disarms.
  * A forward whose plan has no merge launch issues it as its own launch behind the attention kernel (correct, nothing saved).
- * The caller reserves the FIRST token with quest_step_state_advance before the first step; from then on the device state
- * (and its host mirror, InferenceController.prepare_metadata(1) after every step) runs one reserved token ahead of the
+ * The caller reserves the FIRST token with quest_step_state_advance_batched before the first step; from then on the device
+ * state (and its host mirror, InferenceController.prepare_metadata(1) after every step) runs one reserved token ahead of the
  * tokens appended.  state == NULL disarms.  At most 64 sequences. */
 int quest_decode_arm_step_advance(quest_decode_handler_t* h, quest_step_state_t* state, const int32_t* kv_tables,
                                   const int32_t* meta_tables, uint32_t page_size, uint32_t max_kv_pages,
                                   uint32_t max_meta_pages, quest_batch_t batch);
+
+/* quest_append_estimate with lengths / last-page ids / n_out (= state[i].n_pages - 1) taken from `state`.
+ * o is [n_seqs][num_qo_heads][o_stride] with o_stride >= max_n_out, the largest n_out the graph will ever see
+ * (the grid is sized for it; surplus workgroups exit).  tile_max_offset: 0, or the tiles form described below. */
 int quest_append_estimate_batched(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                  uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
+                                  uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out, uint32_t tile_max_offset,
                                   quest_paged_kv_t metadata, const quest_step_state_t* state, quest_batch_t batch,
                                   quest_stream_t stream);
-/* The handler must have been planned for the batch: quest_decode_set_batch(h, n_seqs) before begin_forward. */
+/* quest_decode_forward_fused_topk with the row length (state[i].n_pages - 1) and the current page taken
+ * from `state`; scores is [n_seqs][num_qo_heads][score_stride].  The plan (selected-page count) is the one of
+ * begin_forward and must not exceed state[i].n_pages - 1 for the life of the graph; the handler must have been planned for
+ * the batch: quest_decode_set_batch(h, n_seqs) before begin_forward.  tile_max_offset: 0, or the tiles form. */
 int quest_decode_forward_fused_topk_batched(quest_decode_handler_t* h, const void* q, void* o,
                                             quest_paged_kv_t paged_kv, uint32_t num_qo_heads, const void* scores,
-                                            uint32_t score_stride, uint32_t max_n_scores,
+                                            uint32_t score_stride, uint32_t max_n_scores, uint32_t tile_max_offset,
                                             const quest_step_state_t* state, quest_batch_t batch, float* lse,
                                             quest_stream_t stream);
 /*
- * The tiles pair (quest_append_estimate_tiles_dyn / quest_decode_forward_fused_topk_tiles_dyn above) for n_seqs sequences
- * in one launch each: the same device code, of which the _tiles_dyn pair is the n_seqs == 1 case.  o / scores are
- * [n_seqs][num_qo_heads][stride]; every row carries its own tile maxima at tile_max_offset (= max_n rounded up to 8; rows
- * 16-byte aligned: base 16-byte aligned and stride a multiple of 8 with stride >= tile_max_offset + ceil(max_n / 8)
- * rounded up to 4).  All sequences share the capacity max_n; sequence i's live row (state[i].n_pages - 1 columns) may be
- * shorter, down to empty: only the maxima of its live runs of 8 pages are written and read, whatever lies behind them in
- * the row is never looked at.  Per-sequence budgets (batch.page_budgets), a sequence shorter than its budget (it attends
- * all of its pages) and quest_decode_set_selection_out work as in the whole-row batched pair.  Selections and outputs are
- * those of quest_append_estimate_batched + quest_decode_forward_fused_topk_batched under the same plan, bit for bit.
- * QUEST_EINVAL: tile_max_offset == 0 or not max_n rounded up to 8, a stride without room for the maxima, misaligned
- * rows, n_seqs == 0, a KV table stride shorter than max_n + 1 or a metadata table that does not cover max_n (n_seqs > 1).
+ * THE TILES FORM of the pair above (tile_max_offset != 0), for LONG score rows (round 5; cfg 4: 8191 pages), with TILE
+ * MAXIMA handed across the kernel boundary: the estimate workgroup that holds the scores of 8 consecutive pages also stores
+ * the largest of them (as an order-preserving 16-bit key) at o[i][h][tile_max_offset + page / 8], and the attention launch
+ * selects in two short passes -- the top-k TILES by maximum (a sufficient candidate set under the declared tie rule:
+ * csrc/decode_device.cuh sparse_decode_tiles_body), then the exact top-k over those tiles' 8 k scores -- instead of passes
+ * over the whole row in every workgroup of a head.  Selections and outputs are those of the whole-row form
+ * (tile_max_offset 0) under the same plan, bit for bit.
+ * Row layout: every row carries its own tile maxima at tile_max_offset = max_n rounded up to 8; rows 16-byte aligned (base
+ * 16-byte aligned and stride a multiple of 8) with stride >= tile_max_offset + ceil(max_n / 8) rounded up to 4.  All
+ * sequences share the capacity max_n; sequence i's live row (state[i].n_pages - 1 columns) may be shorter, down to empty:
+ * only the maxima of its live runs of 8 pages are written and read, whatever lies behind them in the row is never looked
+ * at.  Per-sequence budgets (batch.page_budgets), a sequence shorter than its budget (it attends all of its pages) and
+ * quest_decode_set_selection_out work as in the whole-row form.
+ * QUEST_EINVAL: tile_max_offset not max_n rounded up to 8, a stride without room for the maxima, misaligned rows,
+ * n_seqs == 0, a KV table stride shorter than max_n + 1 or a metadata table that does not cover max_n (n_seqs > 1).
  * QUEST_ESTATE: no plan, or a plan for fewer sequences.  QUEST_EUNSUPPORTED, before anything is launched: page size other
- * than 16, more than 256 selected pages, rows beyond 16384 pages, an estimate shape with no tile 8 pages wide -- the
- * caller then issues the whole-row pair.  quest_decode_last_launch_info reports front-end variant 8 and n_seqs.
+ * than 16, more than 256 selected pages, rows beyond 16384 pages, an estimate shape with no tile 8 pages wide (the
+ * estimate side needs its workgroup tile to be a multiple of 8 pages wide; head_dim 256: the tile covers 4 kv heads instead
+ * of 8) -- the caller then issues the whole-row form.  quest_decode_last_launch_info reports front-end variant 8 and n_seqs.
  */
-int quest_append_estimate_tiles_batched(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                        uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
-                                        uint32_t tile_max_offset, quest_paged_kv_t metadata,
-                                        const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream);
-int quest_decode_forward_fused_topk_tiles_batched(quest_decode_handler_t* h, const void* q, void* o,
-                                                  quest_paged_kv_t paged_kv, uint32_t num_qo_heads, const void* scores,
-                                                  uint32_t score_stride, uint32_t max_n_scores, uint32_t tile_max_offset,
-                                                  const quest_step_state_t* state, quest_batch_t batch, float* lse,
-                                                  quest_stream_t stream);
+
+/* quest_append_kv_cache_decode with lengths / last-page ids from `state` (dense layers of a replayed step). */
 int quest_append_kv_cache_decode_batched(const void* k, const void* v, quest_paged_kv_t kv, quest_paged_kv_t metadata,
                                          const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream);
+/* quest_decode_forward_shared over ALL pages of every sequence (state[i].n_pages - 1 listed pages + the current
+ * one): paged_kv.indices = the full page tables.  Plan with begin_forward(n_selected_pages = pool capacity - 1);
+ * workgroups past the live length contribute empty partial states. */
 int quest_decode_forward_shared_batched(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,
                                         uint32_t num_qo_heads, const quest_step_state_t* state, quest_batch_t batch,
                                         float* lse, quest_stream_t stream);
-/* quest_decode_append_forward_shared_dyn for every sequence of the batch (k, v: [n_seqs][kv heads][head_dim]). */
+/* quest_append_kv_cache_decode_batched + quest_decode_forward_shared_batched in ONE launch (round 4: a full-KV layer of a
+ * captured step = attention + merge instead of append + attention + merge; the reference's pair of calls is
+ * QuestAttention.py:106 and :125-132 / page.cu:6-99).  k, v: the new tokens [n_seqs][kv heads][head_dim], not yet in the
+ * pool: the one workgroup per kv head that attends the current page takes the row from k / v, writes it to the pool and
+ * folds k into the page's (max, min) metadata entry -- same pool bytes as the separate append.  metadata: the layer's
+ * metadata pool (same geometry as the KV pool; lengths from `state`).  QUEST_EUNSUPPORTED for shapes outside the
+ * group-shared kernel (page_size 16, head_dim 64 / 128): issue the two launches then. */
 int quest_decode_append_forward_shared_batched(quest_decode_handler_t* h, const void* k, const void* v,
                                                quest_paged_kv_t metadata, const void* q, void* o,
                                                quest_paged_kv_t paged_kv, uint32_t num_qo_heads,
@@ -430,7 +369,7 @@ int quest_decode_layer_fused_batched(quest_decode_handler_t* h, const void* k, c
  *              batch.page_budgets is NULL;
  *   attention: per (sequence, head) over indices[i][h][0 .. k_i) + the current page; plan the handler with
  *              begin_forward(n_selected_pages = max_i budget_i - 1) after quest_decode_set_batch.
- * Same bits as the single-sequence operators on each sequence.
+ * Same bits as the eager operators on each sequence.
  */
 int quest_estimate_attn_score_batched(const void* q, void* o, uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
                                       quest_paged_kv_t metadata, const quest_step_state_t* state, quest_batch_t batch,
@@ -442,50 +381,12 @@ int quest_topk_filtering_batched(const void* scores, uint32_t score_stride, uint
 int quest_decode_forward_batched(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,
                                  uint32_t num_qo_heads, const int32_t* indices, uint32_t idx_stride,
                                  const quest_step_state_t* state, quest_batch_t batch, float* lse, quest_stream_t stream);
-/* q: [n_seqs][num_qo_heads][dim], k: [n_seqs][num_kv_heads][dim]; row i sits at position state[i].seq_len - 1. */
-int quest_apply_rope_in_place_batched(void* q, void* k, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                                      uint32_t head_dim, float rope_scale, float rope_theta,
-                                      const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream);
 /* Element type of the pools / q / o this handler's forwards serve (QUEST_DTYPE_*; default QUEST_DTYPE_F16).  Every forward
  * checks its view's dtype against it (QUEST_EINVAL).  May be called at any time between forwards; the plan and the fp32
  * workspace do not depend on it.  QUEST_EINVAL for an unknown value. */
 int quest_decode_set_dtype(quest_decode_handler_t* h, uint32_t dtype);
 /* Sequences per launch the next begin_forward plans (workspace, work split) for; default 1. */
 int quest_decode_set_batch(quest_decode_handler_t* h, uint32_t n_seqs);
-
-/* Introspection of the current plan (for benches/tests): pages per workgroup, workgroups per head. */
-int quest_decode_plan_info(const quest_decode_handler_t* h, uint32_t* pages_per_chunk,
-                           uint32_t* chunks_per_head);
-/* Which kernel instantiation the handler's most recent per-head-list launch (quest_decode_forward*, fused or not) took:
- * info = {keys per thread of the fused top-k front end (0: index-tensor launch), waves per workgroup, front-end variant
- * (0 / 1 / 3: first generation with scalar / vector-fed staging arrays / keys straight into registers; 2: second
- * generation; 8: tiles -- the rows carry tile maxima; 7: the one-launch layer, quest_decode_layer_fused_batched), 1 if the
- * one-variant instantiation was launched (0: the generic kernel), workgroups per head, sequences}.  Tests and benches
- * assert with it that they run the kernel they mean to. */
-int quest_decode_last_launch_info(const quest_decode_handler_t* h, uint32_t info[6]);
-/* Developer aid: the handler's partial-state workspace ([sequences][heads][workgroups per head][record_floats] fp32:
- * acc[head_dim], m, d, spare).  Builds with -DQUEST_WALLSTAMPS leave per-workgroup wall-clock stamps in the spare words
- * (scripts/wallstamps.py). */
-int quest_decode_debug_workspace(const quest_decode_handler_t* h, void** ptr, uint64_t* bytes, uint32_t* record_floats);
-/* Measurement aid: with skip != 0, quest_decode_forward* launch only the attention kernel and leave the
- * per-workgroup partial states in the handler's workspace (the output tensor is NOT written when the plan has
- * more than one workgroup per head).  Lets a bench time the dominant kernel by itself. */
-int quest_decode_set_skip_merge(quest_decode_handler_t* h, int skip);
-/* Inspection aid for the state-driven / batched fused launches (quest_decode_forward_fused_topk_dyn/_batched), which
- * otherwise keep the selected pages inside the kernel: while set, every such launch also writes its selection --
- * values (fp16 scores) to val_out and physical page ids to idx_out, both [n_seqs][num_qo_heads][n_selected_pages of
- * the plan] (rows of a sequence still shorter than the budget are filled up to its live page count).  NULL
- * pointers turn it off.  Not an entry the reference has: its top-k output lives in topk_filtering's tensors. */
-int quest_decode_set_selection_out(quest_decode_handler_t* h, void* val_out, int32_t* idx_out);
-/* Which top-k front end the fused launches use: 0 = automatic (by row length and alignment), 1 = first generation
- * (csrc/topk_select.cuh; rows up to 4096 pages), 2 = second generation (csrc/topk_bitmap.cuh; needs 8-byte aligned
- * score rows) without its histogram pre-filter, 3 = second generation with the pre-filter.  All are slot ownership and
- * implement the same selection: bit-identical page lists and outputs.  Tuning / test aid.  (The tiles front end is chosen
- * by calling quest_decode_forward_fused_topk_tiles_dyn.  Round 4's column-range ownership and third generation measured
- * slower and were removed in round 5.) */
-int quest_decode_set_front_end(quest_decode_handler_t* h, int generation);
-/* Override the planner (0 = automatic).  Used by tuning sweeps. */
-int quest_decode_set_pages_per_chunk(quest_decode_handler_t* h, uint32_t pages_per_chunk);
 
 /*
  * apply_rope_in_place (bsk_ops.h:23-27, page.cu:212-252 -> QKApplyRotaryInPlace,
@@ -496,22 +397,16 @@ int quest_apply_rope_in_place(void* q, void* k, uint32_t n, uint32_t past_kv_len
                               float rope_scale, float rope_theta, quest_stream_t stream);
 
 /*
- * RoPE from a frequency table (EXTENSION: the llama3 and yarn scalings of Hugging Face's modeling_rope_utils, whose
- * frequencies no closed formula in the kernel reproduces bit for bit).  Pair i (features i, i + head_dim/2) at position p
- * rotates by p * inv_freq[i]; cos and sin are multiplied by attention_factor.  inv_freq: device, head_dim/2 fp32.
- * states NULL: row i at past_kv_len + i; else row i at states[i].seq_len - 1 (one row per sequence; past_kv_len unused),
- * so one entry serves the eager, single-state and batched forms.  QUEST_EINVAL for a NULL table or an attention_factor
- * that is not finite and > 0; head_dim 64 / 128 / 256.  The rope_scale / rope_theta entries (default and linear
- * scaling) keep their in-kernel formula.
+ * RoPE for q / k of element type `dtype` (QUEST_DTYPE_*), every form in one entry (EXTENSION).
+ * Frequencies: inv_freq NULL = the rope_scale / rope_theta formula of quest_apply_rope_in_place (attention_factor unused;
+ * default and linear scaling); else a frequency table (the llama3 and yarn scalings of Hugging Face's modeling_rope_utils,
+ * whose frequencies no closed formula in the kernel reproduces bit for bit): pair i (features i, i + head_dim/2) at position
+ * p rotates by p * inv_freq[i]; cos and sin are multiplied by attention_factor; inv_freq: device, head_dim/2 fp32
+ * (rope_scale / rope_theta unused).  QUEST_EINVAL for an attention_factor that is not finite and > 0.
+ * Positions: states NULL = row i at past_kv_len + i; else row i at states[i].seq_len - 1 (n = sequences, one row per
+ * sequence; past_kv_len unused), so one entry serves the eager and the state-driven forms.
+ * head_dim 64 / 128 / 256.  fp32 arithmetic, one rounding to the element type.
  */
-int quest_apply_rope_in_place_freqs(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
-                                    uint32_t num_kv_heads, uint32_t head_dim, const float* inv_freq,
-                                    float attention_factor, const quest_step_state_t* states, quest_stream_t stream);
-
-/* The RoPE entries above for q / k of element type `dtype` (QUEST_DTYPE_*), in one entry: inv_freq NULL = the
- * rope_scale / rope_theta formula of quest_apply_rope_in_place (attention_factor unused), else the table form of
- * quest_apply_rope_in_place_freqs (rope_scale / rope_theta unused); states NULL = rows at past_kv_len + i, else row i at
- * states[i].seq_len - 1 (n = sequences).  fp32 arithmetic, one rounding to the element type. */
 int quest_apply_rope_in_place_dtype(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
                                     uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
                                     const float* inv_freq, float attention_factor, const quest_step_state_t* states,
@@ -563,10 +458,10 @@ int quest_prefill_with_paged_kv_cache(const void* q, void* o, uint32_t n_q, uint
  *   quest_decode_gemv_residual h[out_dim]  += W . x                           (in place on the residual stream)
  *   quest_decode_mlp_gate_up   act[intermediate] = silu(Wg . n) * (Wu . n),   n = rmsnorm(h; gamma, eps)
  *   quest_decode_qkv_rope      q, k, v = Wq . n, Wk . n, Wv . n with rotate-half RoPE on q and k at position
- *                              state->seq_len - 1 (call after quest_step_state_advance), n = rmsnorm(h; gamma, eps);
- *                              default / linear RoPE: frequency (1 / rope_scale) * rope_theta^(-2i / head_dim)
- *   quest_decode_qkv_rope_freqs  the same with the frequency table of quest_apply_rope_in_place_freqs (inv_freq:
- *                              device, head_dim/2 fp32; cos / sin times attention_factor; QUEST_EINVAL like there)
+ *                              state->seq_len - 1 (call after quest_step_state_advance_batched), n = rmsnorm(h; gamma,
+ *                              eps).  inv_freq NULL: default / linear RoPE, frequency (1 / rope_scale) *
+ *                              rope_theta^(-2i / head_dim); else the frequency table and attention_factor of
+ *                              quest_apply_rope_in_place_dtype (QUEST_EINVAL like there)
  */
 int quest_decode_norm_gemv(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
                            uint32_t out_dim, quest_stream_t stream);
@@ -576,19 +471,14 @@ int quest_decode_mlp_gate_up(const void* h, const void* gamma, float eps, const 
                              uint32_t hidden, uint32_t intermediate, quest_stream_t stream);
 int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
                           void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                          uint32_t head_dim, float rope_scale, float rope_theta, const quest_step_state_t* state,
-                          quest_stream_t stream);
-int quest_decode_qkv_rope_freqs(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
-                                void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                                uint32_t head_dim, const float* inv_freq, float attention_factor,
-                                const quest_step_state_t* state, quest_stream_t stream);
+                          uint32_t head_dim, float rope_scale, float rope_theta, const float* inv_freq,
+                          float attention_factor, const quest_step_state_t* state, quest_stream_t stream);
 /*
  * The same four launches for n_tokens <= 16 decode tokens at once -- one per sequence of a batch (the reference asserts
  * batch size 1; BatchedInferenceController): x / h `[n_tokens][in]`, outputs `[n_tokens][out]` (q / k / v
  * `[n_tokens][heads][head_dim]`), all contiguous; `states` = n_tokens consecutive quest_step_state_t records (the batched
  * step state), token i rotated at states[i].seq_len - 1.  The weights are read once for the whole batch (MFMA row-dots:
- * weights = A operand, tokens = the 16 columns of B); head_dim % 16 == 0 for the q/k/v launch, which also comes in the
- * frequency-table form (quest_decode_qkv_rope_batched_freqs, arguments as for quest_decode_qkv_rope_freqs).
+ * weights = A operand, tokens = the 16 columns of B); head_dim % 16 == 0 for the q/k/v launch.
  */
 int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
                                    uint32_t out_dim, uint32_t n_tokens, quest_stream_t stream);
@@ -600,16 +490,12 @@ int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma, float eps
 int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                   const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
                                   uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
-                                  const quest_step_state_t* states, uint32_t n_tokens, quest_stream_t stream);
-int quest_decode_qkv_rope_batched_freqs(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
-                                        const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
-                                        uint32_t num_kv_heads, uint32_t head_dim, const float* inv_freq,
-                                        float attention_factor, const quest_step_state_t* states, uint32_t n_tokens,
-                                        quest_stream_t stream);
+                                  const float* inv_freq, float attention_factor, const quest_step_state_t* states,
+                                  uint32_t n_tokens, quest_stream_t stream);
 
 /* The q-k-v launch without the rotation (fp16), for models whose q and k pass a per-head norm before RoPE: RMSNorm(h) ->
  * q = Wq x [q_rows], k = Wk x, v = Wv x [kv_rows], stored unrotated; quest_apply_qk_norm_rope_in_place_dtype follows.
- * The same row-dots in the same order as quest_decode_qkv_rope* at head_dim <= 256: a lane of the batch-1 kernel adds a
+ * The same row-dots in the same order as quest_decode_qkv_rope / _batched at head_dim <= 256: a lane of the batch-1 kernel adds a
  * row's products in the same order whatever the workgroup shape, and the batched form (n_tokens <= 16) is planned with the
  * rotating launch's LDS budget, so both take the same n-token kernel -- the one
  * quest_decode_batched_plan(hidden, q_rows + 2 kv_rows, n_tokens, 1, ...) names -- and v is bit-identical.  (Beyond
@@ -619,6 +505,45 @@ int quest_decode_qkv(const void* h, const void* gamma, float eps, const void* wq
 int quest_decode_qkv_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
                              void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows,
                              uint32_t n_tokens, quest_stream_t stream);
+
+/*
+ * ---- NOT PART OF THE STABLE SURFACE: introspection and overrides for benches, tests and tuning sweeps.  They may change
+ * with the kernels they look into; an integration calls none of them.
+ */
+
+/* Introspection of the current plan (for benches/tests): pages per workgroup, workgroups per head. */
+int quest_decode_plan_info(const quest_decode_handler_t* h, uint32_t* pages_per_chunk,
+                           uint32_t* chunks_per_head);
+/* Which kernel instantiation the handler's most recent per-head-list launch (quest_decode_forward*, fused or not) took:
+ * info = {keys per thread of the fused top-k front end (0: index-tensor launch), waves per workgroup, front-end variant
+ * (0 / 1 / 3: first generation with scalar / vector-fed staging arrays / keys straight into registers; 2: second
+ * generation; 8: tiles -- the rows carry tile maxima; 7: the one-launch layer, quest_decode_layer_fused_batched), 1 if the
+ * one-variant instantiation was launched (0: the generic kernel), workgroups per head, sequences}.  Tests and benches
+ * assert with it that they run the kernel they mean to. */
+int quest_decode_last_launch_info(const quest_decode_handler_t* h, uint32_t info[6]);
+/* Developer aid: the handler's partial-state workspace ([sequences][heads][workgroups per head][record_floats] fp32:
+ * acc[head_dim], m, d, spare).  Builds with -DQUEST_WALLSTAMPS leave per-workgroup wall-clock stamps in the spare words
+ * (scripts/wallstamps.py). */
+int quest_decode_debug_workspace(const quest_decode_handler_t* h, void** ptr, uint64_t* bytes, uint32_t* record_floats);
+/* Measurement aid: with skip != 0, quest_decode_forward* launch only the attention kernel and leave the
+ * per-workgroup partial states in the handler's workspace (the output tensor is NOT written when the plan has
+ * more than one workgroup per head).  Lets a bench time the dominant kernel by itself. */
+int quest_decode_set_skip_merge(quest_decode_handler_t* h, int skip);
+/* Inspection aid for the state-driven / batched fused launches (quest_decode_forward_fused_topk_batched), which
+ * otherwise keep the selected pages inside the kernel: while set, every such launch also writes its selection --
+ * values (fp16 scores) to val_out and physical page ids to idx_out, both [n_seqs][num_qo_heads][n_selected_pages of
+ * the plan] (rows of a sequence still shorter than the budget are filled up to its live page count).  NULL
+ * pointers turn it off.  Not an entry the reference has: its top-k output lives in topk_filtering's tensors. */
+int quest_decode_set_selection_out(quest_decode_handler_t* h, void* val_out, int32_t* idx_out);
+/* Which top-k front end the fused launches use: 0 = automatic (by row length and alignment), 1 = first generation
+ * (csrc/topk_select.cuh; rows up to 4096 pages), 2 = second generation (csrc/topk_bitmap.cuh; needs 8-byte aligned
+ * score rows) without its histogram pre-filter, 3 = second generation with the pre-filter.  All are slot ownership and
+ * implement the same selection: bit-identical page lists and outputs.  Tuning / test aid.  (The tiles front end is chosen
+ * by the launch's tile_max_offset.  Round 4's column-range ownership and third generation measured
+ * slower and were removed in round 5.) */
+int quest_decode_set_front_end(quest_decode_handler_t* h, int generation);
+/* Override the planner (0 = automatic).  Used by tuning sweeps. */
+int quest_decode_set_pages_per_chunk(quest_decode_handler_t* h, uint32_t pages_per_chunk);
 
 /* Which kernel an n-token launch of this shape takes (tests / tuning; nothing is launched): 1 and info = {k slices per
  * quad of rows, rounds, dynamic LDS bytes, workgroups, 128-wide k steps per row, weight fragments per set} for the persistent

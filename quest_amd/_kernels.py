@@ -138,16 +138,13 @@ def apply_rope_in_place(q, k, past_kv_len: int, rope_scale: float, rope_theta: f
     _check_eq(q.size(0), k.size(0), "q.size(0), k.size(0)")
     _check_eq(q.size(2), k.size(2), "q.size(2), k.size(2)")
     _check_half(q, "apply_rope_in_place", k)
-    if q.dtype != torch.float16:
-        return _rope_typed(q, k, q.size(0), past_kv_len, rope_scale, rope_theta, None, 1.0, None, "apply_rope_in_place")
-    check(lib.quest_apply_rope_in_place(q.data_ptr(), k.data_ptr(), q.size(0), int(past_kv_len), q.size(1),
-                                        k.size(1), q.size(2), float(rope_scale), float(rope_theta), _stream(q)),
-          "apply_rope_in_place")
+    _rope_typed(q, k, q.size(0), past_kv_len, rope_scale, rope_theta, None, 1.0, None, "apply_rope_in_place")
 
 
 def _rope_typed(q, k, n: int, past_kv_len: int, rope_scale: float, rope_theta: float, inv_freq, attention_factor: float,
                 states, what: str) -> None:
-    """The RoPE forms for q / k that are not fp16: the one typed entry of the C ABI (quest_apply_rope_in_place_dtype)."""
+    """Every RoPE form (formula or frequency table, eager or state-driven positions, fp16 or bf16): the one typed entry of
+    the C ABI (quest_apply_rope_in_place_dtype)."""
     check(lib.quest_apply_rope_in_place_dtype(q.data_ptr(), k.data_ptr(), int(n), int(past_kv_len), q.size(1), k.size(1),
                                               q.size(2), float(rope_scale), float(rope_theta),
                                               inv_freq.data_ptr() if inv_freq is not None else None,
@@ -179,13 +176,7 @@ def apply_rope_in_place_freqs(q, k, inv_freq, attention_factor: float, past_kv_l
     if states is not None:
         _check_input(states, "states")
         _check_eq(states.numel(), q.size(0) * STEP_STATE_INTS, "states.numel(), n * 8")
-    if q.dtype != torch.float16:
-        return _rope_typed(q, k, q.size(0), past_kv_len, 1.0, 1.0, inv_freq, attention_factor, states,
-                           "apply_rope_in_place_freqs")
-    check(lib.quest_apply_rope_in_place_freqs(q.data_ptr(), k.data_ptr(), q.size(0), int(past_kv_len), q.size(1),
-                                              k.size(1), q.size(2), inv_freq.data_ptr(), float(attention_factor),
-                                              states.data_ptr() if states is not None else None, _stream(q)),
-          "apply_rope_in_place_freqs")
+    _rope_typed(q, k, q.size(0), past_kv_len, 1.0, 1.0, inv_freq, attention_factor, states, "apply_rope_in_place_freqs")
 
 
 def apply_qk_norm_rope_in_place(q, k, q_weight, k_weight, eps: float, past_kv_len: int = 0, rope_scale: float = 1.0,
@@ -251,11 +242,9 @@ def topk_filtering(estimated_value, estimated_indices, d_out, indices_out, buf, 
     _check_eq(page_budget, d_out.size(1), "page_budget, d_out.size(1)")
     _check_eq(page_budget, indices_out.size(1), "page_budget, indices_out.size(1)")
     _check_half(estimated_value, "Top-k filtering", d_out)  # (the selection orders 16-bit patterns: one code for both types)
-    check(lib.quest_topk_filtering_strided(estimated_value.data_ptr(), estimated_value.stride(0), estimated_indices.data_ptr(),
-                                           d_out.data_ptr(), indices_out.data_ptr(),
-                                           buf.data_ptr() if buf is not None else None, num_heads, num_pages,
-                                           int(page_budget), _stream(estimated_value)),
-          "Top-k filtering")
+    check(lib.quest_topk_filtering(estimated_value.data_ptr(), estimated_value.stride(0), estimated_indices.data_ptr(),
+                                   d_out.data_ptr(), indices_out.data_ptr(), buf.data_ptr() if buf is not None else None,
+                                   num_heads, num_pages, int(page_budget), _stream(estimated_value)), "Top-k filtering")
 
 
 def estimate_attn_score(q, o, metadata_data, metadata_indices, metadata_indptr, metadata_last_page_len: int,
@@ -345,8 +334,8 @@ def append_estimate(k, v, kv_data, kv_indices, kv_indptr, kv_last_page_len: int,
     kv = _paged(kv_data, kv_indices, kv_indptr, kv_last_page_len, kv_last_page_idx, layout)
     meta = _paged(metadata_data, metadata_indices, metadata_indptr, metadata_last_page_len, metadata_last_page_idx,
                   layout)
-    check(lib.quest_append_estimate_strided(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1),
-                                            o.size(1), o.stride(0), meta, _stream(k)), "append_estimate")
+    check(lib.quest_append_estimate(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1), o.size(1),
+                                    o.stride(0), meta, _stream(k)), "append_estimate")
 
 
 # ---- decode-token projections of a decoder layer, fused (EXTENSION: csrc/decode_layer.hip)
@@ -435,7 +424,7 @@ def decode_qkv_rope(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, ro
     """q ``[1, Hq, D]``, k / v ``[1, Hkv, D]`` = projections of ``rmsnorm(h; gamma, eps)`` with RoPE on q and k at the
     position ``state.seq_len - 1`` (the device-resident step state, after ``step_state_advance_batched``)."""
     args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, state, 1)
-    check(lib.quest_decode_qkv_rope(*args, float(rope_scale), float(rope_theta), state.data_ptr(), _stream(h)),
+    check(lib.quest_decode_qkv_rope(*args, float(rope_scale), float(rope_theta), None, 1.0, state.data_ptr(), _stream(h)),
           "decode_qkv_rope")
 
 
@@ -444,8 +433,8 @@ def decode_qkv_rope_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: i
     """``decode_qkv_rope`` with the RoPE frequency table of ``apply_rope_in_place_freqs`` (llama3 / yarn)."""
     args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, state, 1)
     _check_rope_table(inv_freq, head_dim)
-    check(lib.quest_decode_qkv_rope_freqs(*args, inv_freq.data_ptr(), float(attention_factor), state.data_ptr(),
-                                          _stream(h)), "decode_qkv_rope_freqs")
+    check(lib.quest_decode_qkv_rope(*args, 1.0, 1.0, inv_freq.data_ptr(), float(attention_factor), state.data_ptr(),
+                                    _stream(h)), "decode_qkv_rope_freqs")
 
 
 def decode_qkv(h, gamma, eps: float, wq, wk, wv, q, k, v) -> None:
@@ -514,7 +503,7 @@ def decode_qkv_rope_batched(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim:
     n = h.numel() // wq.size(1)
     _check_tokens(n)
     args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, states, n)
-    check(lib.quest_decode_qkv_rope_batched(*args, float(rope_scale), float(rope_theta), states.data_ptr(), n,
+    check(lib.quest_decode_qkv_rope_batched(*args, float(rope_scale), float(rope_theta), None, 1.0, states.data_ptr(), n,
                                             _stream(h)), "decode_qkv_rope_batched")
 
 
@@ -525,8 +514,8 @@ def decode_qkv_rope_batched_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, hea
     _check_tokens(n)
     args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, states, n)
     _check_rope_table(inv_freq, head_dim)
-    check(lib.quest_decode_qkv_rope_batched_freqs(*args, inv_freq.data_ptr(), float(attention_factor), states.data_ptr(),
-                                                  n, _stream(h)), "decode_qkv_rope_batched_freqs")
+    check(lib.quest_decode_qkv_rope_batched(*args, 1.0, 1.0, inv_freq.data_ptr(), float(attention_factor),
+                                            states.data_ptr(), n, _stream(h)), "decode_qkv_rope_batched_freqs")
 
 
 def decode_qkv_batched(h, gamma, eps: float, wq, wk, wv, q, k, v) -> None:
@@ -623,13 +612,12 @@ def append_estimate_batched(k, v, kv_data, kv_tables, q, o, metadata_data, meta_
     meta = _paged(metadata_data, meta_tables, None, 1, 0, layout)
     if tiles:
         _check_ge(o.size(2), tiles_row_stride(max_n_out), "o.size(2), tiles_row_stride(max_n_out)")
-        return _launched(lib.quest_append_estimate_tiles_batched(
-            k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1), o.size(2), int(max_n_out),
-            tile_max_offset(max_n_out), meta, state.data_ptr(), b, _stream(k)), "append_estimate_batched")
-    check(lib.quest_append_estimate_batched(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1),
-                                            o.size(2), int(max_n_out), meta, state.data_ptr(), b, _stream(k)),
-          "append_estimate_batched")
-    return True
+    code = lib.quest_append_estimate_batched(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1), o.size(2),
+                                             int(max_n_out), tile_max_offset(max_n_out) if tiles else 0, meta,
+                                             state.data_ptr(), b, _stream(k))
+    if not tiles:  # whole rows are the caller's last route: QUEST_EUNSUPPORTED raises
+        check(code, "append_estimate_batched")
+    return _launched(code, "append_estimate_batched")
 
 
 def append_estimate_dyn(k, v, kv_data, kv_table, q, o, metadata_data, meta_table, state, max_n_out: int,
@@ -701,11 +689,7 @@ def apply_rope_in_place_batched(q, k, rope_scale: float, rope_theta: float, stat
     _check_eq(q.size(0), b.n_seqs, "q.size(0), n_seqs")
     _check_eq(k.size(0), b.n_seqs, "k.size(0), n_seqs")
     _check_half(q, "apply_rope_in_place", k)
-    if q.dtype != torch.float16:
-        return _rope_typed(q, k, b.n_seqs, 0, rope_scale, rope_theta, None, 1.0, state, "apply_rope_in_place_batched")
-    check(lib.quest_apply_rope_in_place_batched(q.data_ptr(), k.data_ptr(), q.size(1), k.size(1), q.size(2),
-                                                float(rope_scale), float(rope_theta), state.data_ptr(), b,
-                                                _stream(q)), "apply_rope_in_place_batched")
+    _rope_typed(q, k, b.n_seqs, 0, rope_scale, rope_theta, None, 1.0, state, "apply_rope_in_place_batched")
 
 
 def prefill_with_paged_kv_cache(q, kv_data, kv_indices, kv_last_page_len: int, causal: bool, layout: int,
@@ -838,7 +822,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         self._check_dtype(q, o, paged_kv_data, scores)
         kv = _paged(paged_kv_data, page_table, None, paged_kv_last_page_len, paged_kv_last_page_idx, self._layout)
         # (QUEST_EUNSUPPORTED: chunk larger than the fused front end stages)
-        return _launched(lib.quest_decode_forward_fused_topk_strided(
+        return _launched(lib.quest_decode_forward_fused_topk(
             self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), scores.data_ptr(), scores.size(1), scores.stride(0),
             topk_val_out.data_ptr() if topk_val_out is not None else None,
             topk_idx_out.data_ptr() if topk_idx_out is not None else None, None, _stream(q)), "BatchDecodeWithPagedKVCache")
@@ -929,14 +913,12 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
         if tiles:
             _check_ge(scores.size(2), tiles_row_stride(max_n_scores), "scores.size(2), tiles_row_stride(max_n_scores)")
-            return _launched(lib.quest_decode_forward_fused_topk_tiles_batched(
-                self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), scores.data_ptr(), scores.size(2), int(max_n_scores),
-                tile_max_offset(max_n_scores), state.data_ptr(), b, None, _stream(q)), "BatchDecodeWithPagedKVCache")
-        check(lib.quest_decode_forward_fused_topk_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
-                                                          scores.data_ptr(), scores.size(2), int(max_n_scores),
-                                                          state.data_ptr(), b, None, _stream(q)),
-              "BatchDecodeWithPagedKVCache")
-        return True
+        code = lib.quest_decode_forward_fused_topk_batched(
+            self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), scores.data_ptr(), scores.size(2), int(max_n_scores),
+            tile_max_offset(max_n_scores) if tiles else 0, state.data_ptr(), b, None, _stream(q))
+        if not tiles:  # whole rows are the caller's last route: QUEST_EUNSUPPORTED raises
+            check(code, "BatchDecodeWithPagedKVCache")
+        return _launched(code, "BatchDecodeWithPagedKVCache")
 
     def forward_fused_topk_dyn(self, q, o, paged_kv_data, page_table, scores, state, max_n_scores: int,
                                tiles: bool = False) -> bool:

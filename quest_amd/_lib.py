@@ -47,52 +47,28 @@ SIGNATURES = {
     "quest_append_kv_cache_decode": (ctypes.c_int, [c_vp, c_vp, PagedKV, PagedKV, c_vp]),
     "quest_append_kv_cache_prefill": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, PagedKV, PagedKV, c_vp]),
     "quest_estimate_attn_score": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, PagedKV, c_vp]),
-    "quest_append_estimate": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, PagedKV, c_vp]),
-    "quest_append_estimate_strided": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, c_u32, PagedKV, c_vp]),
-    "quest_topk_filtering": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
-    "quest_topk_filtering_strided": (ctypes.c_int, [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
+    "quest_append_estimate": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, c_u32, PagedKV, c_vp]),
+    "quest_topk_filtering": (ctypes.c_int, [c_vp, c_u32, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
     "quest_decode_handler_create": (ctypes.c_int, [ctypes.POINTER(c_vp), c_u32]),
     "quest_decode_handler_destroy": (None, [c_vp]),
     "quest_decode_begin_forward": (ctypes.c_int, [c_vp, c_u32, c_u32, c_u32, c_u32, c_u32, c_vp]),
     "quest_decode_end_forward": (ctypes.c_int, [c_vp]),
     "quest_decode_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_vp]),
     "quest_decode_forward_shared": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_vp]),
-    "quest_decode_forward_fused_topk": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_vp, c_vp,
+    "quest_decode_forward_fused_topk": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_u32, c_vp, c_vp,
                                                         c_vp, c_vp]),
-    "quest_decode_forward_fused_topk_strided": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_u32, c_vp,
-                                                                c_vp, c_vp, c_vp]),
-    "quest_step_state_advance": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
-    "quest_append_estimate_dyn": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, c_u32, PagedKV, c_vp,
-                                                  c_vp]),
-    "quest_decode_forward_fused_topk_dyn": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_u32, c_vp,
-                                                            c_vp, c_vp]),
-    "quest_append_estimate_tiles_dyn": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, PagedKV,
-                                                        c_vp, c_vp]),
-    "quest_decode_forward_fused_topk_tiles_dyn": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_u32, c_u32,
-                                                                  c_vp, c_vp, c_vp]),
-    "quest_append_kv_cache_decode_dyn": (ctypes.c_int, [c_vp, c_vp, PagedKV, PagedKV, c_vp, c_vp]),
-    "quest_decode_append_forward_shared_dyn": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_vp, c_vp, PagedKV, c_u32, c_vp, c_vp,
-                                                              c_vp]),
     "quest_decode_append_forward_shared_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_vp, c_vp, PagedKV, c_u32, c_vp,
                                                                   Batch, c_vp, c_vp]),
-    "quest_decode_forward_shared_dyn": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_vp, c_vp]),
-    "quest_apply_rope_in_place_dyn": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, c_u32, c_f32, c_f32, c_vp, c_vp]),
     "quest_step_state_advance_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, Batch, c_vp]),
     "quest_decode_arm_step_advance": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, Batch]),
-    "quest_append_estimate_batched": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, c_u32, PagedKV,
+    "quest_append_estimate_batched": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, PagedKV,
                                                       c_vp, Batch, c_vp]),
-    "quest_decode_forward_fused_topk_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_u32,
+    "quest_decode_forward_fused_topk_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_u32, c_u32,
                                                                 c_vp, Batch, c_vp, c_vp]),
-    "quest_append_estimate_tiles_batched": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32,
-                                                            PagedKV, c_vp, Batch, c_vp]),
-    "quest_decode_forward_fused_topk_tiles_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, c_u32, c_u32,
-                                                                      c_u32, c_vp, Batch, c_vp, c_vp]),
     "quest_decode_layer_fused_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_vp, c_vp, PagedKV, c_u32, c_u32, c_vp,
                                                          Batch, c_vp, c_u32, c_vp, c_vp]),
     "quest_append_kv_cache_decode_batched": (ctypes.c_int, [c_vp, c_vp, PagedKV, PagedKV, c_vp, Batch, c_vp]),
     "quest_decode_forward_shared_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, PagedKV, c_u32, c_vp, Batch, c_vp, c_vp]),
-    "quest_apply_rope_in_place_batched": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, c_u32, c_f32, c_f32, c_vp, Batch,
-                                                          c_vp]),
     "quest_estimate_attn_score_batched": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, c_u32, PagedKV, c_vp, Batch, c_vp]),
     "quest_topk_filtering_batched": (ctypes.c_int, [c_vp, c_u32, c_u32, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp, Batch,
                                                      c_vp]),
@@ -115,18 +91,12 @@ SIGNATURES = {
     "quest_decode_gemv_residual": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp]),
     "quest_decode_mlp_gate_up": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp]),
     "quest_decode_qkv_rope": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32,
-                                              c_u32, c_f32, c_f32, c_vp, c_vp]),
+                                              c_u32, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp]),
     "quest_decode_norm_gemv_batched": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
     "quest_decode_gemv_residual_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
     "quest_decode_mlp_gate_up_batched": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
     "quest_decode_qkv_rope_batched": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32,
-                                                      c_u32, c_u32, c_f32, c_f32, c_vp, c_u32, c_vp]),
-    "quest_apply_rope_in_place_freqs": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_u32, c_vp, c_f32, c_vp,
-                                                        c_vp]),
-    "quest_decode_qkv_rope_freqs": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32,
-                                                    c_u32, c_u32, c_vp, c_f32, c_vp, c_vp]),
-    "quest_decode_qkv_rope_batched_freqs": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32,
-                                                            c_u32, c_u32, c_u32, c_vp, c_f32, c_vp, c_u32, c_vp]),
+                                                      c_u32, c_u32, c_f32, c_f32, c_vp, c_f32, c_vp, c_u32, c_vp]),
     "quest_apply_qk_norm_rope_in_place_dtype": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_u32, c_vp, c_vp,
                                                                 c_f32, c_f32, c_f32, c_vp, c_f32, c_vp, c_u32, c_vp]),
     "quest_decode_qkv": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),

@@ -170,13 +170,6 @@ extern "C" int quest_append_kv_cache_decode(const void* k, const void* v, quest_
     return append_decode(k, v, kv, metadata, nullptr, 1, stream);
 }
 
-extern "C" int quest_append_kv_cache_decode_dyn(const void* k, const void* v, quest_paged_kv_t kv,
-                                                quest_paged_kv_t metadata, const quest_step_state_t* state,
-                                                quest_stream_t stream) {
-    if (!state) return QUEST_EINVAL;
-    return append_decode(k, v, kv, metadata, state, 1, stream);
-}
-
 extern "C" int quest_append_kv_cache_decode_batched(const void* k, const void* v, quest_paged_kv_t kv,
                                                     quest_paged_kv_t metadata, const quest_step_state_t* state,
                                                     quest_batch_t batch, quest_stream_t stream) {
@@ -206,26 +199,15 @@ extern "C" int quest_append_kv_cache_prefill(const void* k, const void* v, uint3
     return 0;
 }
 
-static int step_state_advance(quest_step_state_t* state, const int32_t* kv_tables, const int32_t* meta_tables, uint32_t page_size,
-                              uint32_t max_kv_pages, uint32_t max_meta_pages, quest_batch_t batch, quest_stream_t stream) {
+extern "C" int quest_step_state_advance_batched(quest_step_state_t* state, const int32_t* kv_tables,
+                                                const int32_t* meta_tables, uint32_t page_size, uint32_t max_kv_pages,
+                                                uint32_t max_meta_pages, quest_batch_t batch, quest_stream_t stream) {
+    if (batch.n_seqs == 0 || batch.kv_table_stride < max_kv_pages || batch.meta_table_stride < max_meta_pages)
+        return QUEST_EINVAL;
     if (!state || !kv_tables || !meta_tables || page_size == 0 || max_kv_pages == 0 || max_meta_pages == 0)
         return QUEST_EINVAL;
     hipLaunchKernelGGL(step_state_advance_kernel, dim3((batch.n_seqs + 63) / 64), dim3(64), 0, (hipStream_t)stream,
                        state, kv_tables, meta_tables, page_size, max_kv_pages, max_meta_pages, batch);
     QUEST_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int quest_step_state_advance(quest_step_state_t* state, const int32_t* kv_table, const int32_t* meta_table,
-                                        uint32_t page_size, uint32_t max_kv_pages, uint32_t max_meta_pages,
-                                        quest_stream_t stream) {
-    return step_state_advance(state, kv_table, meta_table, page_size, max_kv_pages, max_meta_pages, {1, 0, 0, 0}, stream);
-}
-
-extern "C" int quest_step_state_advance_batched(quest_step_state_t* state, const int32_t* kv_tables,
-                                                const int32_t* meta_tables, uint32_t page_size, uint32_t max_kv_pages,
-                                                uint32_t max_meta_pages, quest_batch_t batch, quest_stream_t stream) {
-    if (batch.n_seqs == 0 || batch.kv_table_stride < max_kv_pages || batch.meta_table_stride < max_meta_pages)
-        return QUEST_EINVAL;
-    return step_state_advance(state, kv_tables, meta_tables, page_size, max_kv_pages, max_meta_pages, batch, stream);
 }

@@ -7,16 +7,6 @@
 
 namespace quest {
 
-// K/V tile loads of the per-head-list kernel: streaming (`nt`) by default; -DQUEST_KV_CACHED keeps them in the L2's normal
-// replacement order (tuning: GQA heads of a group re-read each other's pages)
-__device__ __forceinline__ half8 ld8_kv(const half_t* p) {
-#ifdef QUEST_KV_CACHED
-    return ld8(p);
-#else
-    return ld8_stream(p);
-#endif
-}
-
 constexpr float kNegFloor = -1.0e30f;  // finite "-inf": exp2(floor - floor) stays finite, weights it carries are 0
 
 struct DecodeParams {
@@ -309,14 +299,17 @@ __device__ __forceinline__ void attend_slots(const AttendArgs p, const SeqView s
                 left[T_ + t] = len1 - t * R;
                 // rows past the page's length exist in the pool (the page is allocated) but hold
                 // stale bytes; they are fetched only for the sequence's last page and masked in fold
-                k[t] = ld8_kv(b0 + uni[t] + lane_off);
-                v[t] = ld8_kv(b0 + uni[t] + lane_off + v_off);
+                // (streaming loads: keeping the K/V tiles in the L2's normal replacement order, for GQA heads that re-read each
+                // other's pages, was tried with the XCD-aware grid order of commit 8bb0709 and did not win; no profile file
+                // was kept; the build switch was last in the tree at faef74b)
+                k[t] = ld8_stream(b0 + uni[t] + lane_off);
+                v[t] = ld8_stream(b0 + uni[t] + lane_off + v_off);
             }
             if (has1) {  // wave-uniform (a likely-taken hint here cost 3.5 us per batched launch: measured, r3j)
 #pragma unroll
                 for (int t = 0; t < T_; ++t) {
-                    k[T_ + t] = ld8_kv(b1 + uni[t] + lane_off);
-                    v[T_ + t] = ld8_kv(b1 + uni[t] + lane_off + v_off);
+                    k[T_ + t] = ld8_stream(b1 + uni[t] + lane_off);
+                    v[T_ + t] = ld8_stream(b1 + uni[t] + lane_off + v_off);
                 }
                 if constexpr (APPEND) {
                     if (s0 >= n_listed || s1 >= n_listed) {  // wave-uniform: one of the two is the current page
@@ -687,7 +680,7 @@ __device__ __forceinline__ void sparse_decode_body(DecodeParams p, const uint32_
 }
 
 // ---- tiles front end (round 5): long score rows whose producer also left TILE MAXIMA -- per run of 8 columns the largest
-// key of the run (quest_append_estimate_tiles_dyn: the estimate workgroup that holds those 8 scores writes it beside the
+// key of the run (quest_append_estimate_batched's tiles form: the estimate workgroup that holds those 8 scores writes it beside the
 // row).  Two passes of the SAME selection routine instead of four issue-bound passes over 16-32 keys per thread:
 //   1. top-k1 of the row's ceil(n / 8) tile keys, k1 = min(k, tiles), under the declared tie rule (lowest tile first among
 //      equal maxima).  These k1 tiles are a sufficient candidate set: with B = the k1-th largest maximum, at least k scores
@@ -700,7 +693,7 @@ __device__ __forceinline__ void sparse_decode_body(DecodeParams p, const uint32_
 //      short-row selection over <= 4 keys per thread with the validity mask -- same threshold, same ties, same slots as the
 //      selection over the whole row (tests/test_gpu_long_rows.py, test_gpu_full_size.py cfg 4).
 // Serves k <= 256 (two threads per candidate tile at 512 threads) and rows up to 16384 columns (4 tile keys per thread).
-// One sequence or a batch (`seq` = blockIdx.z; quest_decode_forward_fused_topk_tiles_batched): every quantity below the loads is
+// One sequence or a batch (`seq` = blockIdx.z; quest_decode_forward_fused_topk_batched with tile maxima): every quantity below the loads is
 // the sequence's own -- live row length n, n_tiles, k1 and the budget-clamped n_sel -- while the load addresses depend on the shared
 // capacity only; a tile key beyond the sequence's n_tiles (never written by its estimate) is masked in pass 1, a column beyond n
 // in pass 2.  A sequence with an empty row (one page) or a budget of one page skips both passes and attends its current page.

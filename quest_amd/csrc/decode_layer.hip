@@ -956,16 +956,13 @@ extern "C" int quest_decode_mlp_gate_up(const void* h, const void* gamma, float 
                                    (hipStream_t)stream);
 }
 
-struct RopeArgs {  // rotation of the q-k-v launch: closed form (inv_freq NULL) or a frequency table
-    float rcp_scale, log2_rcp_theta;
-    const float* inv_freq;
-    float attn_factor;
-};
-
+// The rotating q-k-v launch: closed form (inv_freq NULL) or a frequency table, as quest_apply_rope_in_place_dtype.
 // batched: the n-token launch (one state per token), else the single-token one (`states` = the one state)
 static int qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
                     void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
-                    RopeArgs rope, const quest_step_state_t* states, bool batched, uint32_t n_tokens, quest_stream_t stream) {
+                    float rope_scale, float rope_theta, const float* inv_freq, float attention_factor,
+                    const quest_step_state_t* states, bool batched, uint32_t n_tokens, quest_stream_t stream) {
+    if (inv_freq ? bad_rope_table(inv_freq, attention_factor) : (rope_scale == 0.f || rope_theta <= 0.f)) return QUEST_EINVAL;
     if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v || !states) return QUEST_EINVAL;
     if (hidden == 0 || num_qo_heads == 0 || num_kv_heads == 0) return QUEST_EINVAL;
     // one token: a wave's 4 row-dots = two rotation pairs of one head; n tokens: a 16-row block = 8 rotation pairs of ONE
@@ -975,8 +972,9 @@ static int qkv_rope(const void* h, const void* gamma, float eps, const void* wq,
     p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
     p.rows[1] = p.rows[2] = num_kv_heads * head_dim;
     p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
-    p.head_dim = head_dim, p.rcp_scale = rope.rcp_scale, p.log2_rcp_theta = rope.log2_rcp_theta, p.state = states;
-    p.inv_freq = rope.inv_freq, p.attn_factor = rope.attn_factor;
+    p.head_dim = head_dim, p.state = states;
+    p.rcp_scale = inv_freq ? 1.0f : 1.0f / rope_scale, p.log2_rcp_theta = inv_freq ? 0.f : -log2f(rope_theta);
+    p.inv_freq = inv_freq, p.attn_factor = inv_freq ? attention_factor : 1.0f;
     const uint32_t rows = p.rows[0] + p.rows[1] + p.rows[2];
     if (!batched) return launch_gemv<kGvQkvRope>(p, rows, (hipStream_t)stream);
     SkinnyArgs a = skinny_args(p, n_tokens);
@@ -988,20 +986,10 @@ static int qkv_rope(const void* h, const void* gamma, float eps, const void* wq,
 extern "C" int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                      const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
                                      uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
-                                     const quest_step_state_t* state, quest_stream_t stream) {
-    if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
-    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
-                    {1.0f / rope_scale, -log2f(rope_theta), nullptr, 1.0f}, state, false, 0, stream);
-}
-
-extern "C" int quest_decode_qkv_rope_freqs(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
-                                           const void* wv, void* q, void* k, void* v, uint32_t hidden,
-                                           uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
-                                           const float* inv_freq, float attention_factor,
-                                           const quest_step_state_t* state, quest_stream_t stream) {
-    if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
-    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
-                    {1.0f, 0.f, inv_freq, attention_factor}, state, false, 0, stream);
+                                     const float* inv_freq, float attention_factor, const quest_step_state_t* state,
+                                     quest_stream_t stream) {
+    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta,
+                    inv_freq, attention_factor, state, false, 0, stream);
 }
 
 // q, k, v projections WITHOUT the rotation (models with a per-head q/k norm between the projection and RoPE: the norm
@@ -1056,22 +1044,11 @@ extern "C" int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma
 extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                              const void* wv, void* q, void* k, void* v, uint32_t hidden,
                                              uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
-                                             float rope_scale, float rope_theta, const quest_step_state_t* states,
-                                             uint32_t n_tokens, quest_stream_t stream) {
-    if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
-    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
-                    {1.0f / rope_scale, -log2f(rope_theta), nullptr, 1.0f}, states, true, n_tokens, stream);
-}
-
-extern "C" int quest_decode_qkv_rope_batched_freqs(const void* h, const void* gamma, float eps, const void* wq,
-                                                   const void* wk, const void* wv, void* q, void* k, void* v,
-                                                   uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                                                   uint32_t head_dim, const float* inv_freq, float attention_factor,
-                                                   const quest_step_state_t* states, uint32_t n_tokens,
-                                                   quest_stream_t stream) {
-    if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
-    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
-                    {1.0f, 0.f, inv_freq, attention_factor}, states, true, n_tokens, stream);
+                                             float rope_scale, float rope_theta, const float* inv_freq,
+                                             float attention_factor, const quest_step_state_t* states, uint32_t n_tokens,
+                                             quest_stream_t stream) {
+    return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta,
+                    inv_freq, attention_factor, states, true, n_tokens, stream);
 }
 
 extern "C" int quest_decode_qkv_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,

@@ -193,23 +193,6 @@ static AppendTail append_tail(const void* k, const void* v, const quest_paged_kv
     return tail;
 }
 
-static int append_estimate_state(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                 uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
-                                 quest_paged_kv_t metadata, const quest_step_state_t* state, quest_batch_t batch,
-                                 quest_stream_t stream, uint32_t tile_off) {
-    if (int e = check_dtype_pair(kv, metadata)) return e;
-    if (!k || !v || !state || max_n_out == 0 || o_stride < max_n_out || batch.n_seqs == 0) return QUEST_EINVAL;
-    if (tile_off && (tile_off % 8u != 0 || tile_off < ((max_n_out + 7u) & ~7u) ||
-                     o_stride < tile_off + ((((max_n_out + 7u) / 8u) + 3u) & ~3u)))
-        return QUEST_EINVAL;  // the maxima live behind the scores of the same row, readable in 8-byte pieces
-    if (int e = check_pool_pair(kv, metadata, true, false)) return e;
-    AppendTail tail = append_tail(k, v, kv, o_stride);
-    tail.state = state;
-    tail.meta_table_stride = batch.meta_table_stride;
-    tail.tile_off = tile_off;
-    return estimate_entry(q, o, num_qo_heads, max_n_out, metadata, tail, (hipStream_t)stream, batch.n_seqs);
-}
-
 extern "C" int quest_estimate_attn_score_batched(const void* q, void* o, uint32_t num_qo_heads, uint32_t o_stride,
                                                  uint32_t max_n_out, quest_paged_kv_t metadata,
                                                  const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream) {
@@ -225,62 +208,38 @@ extern "C" int quest_estimate_attn_score_batched(const void* q, void* o, uint32_
     return estimate_entry(q, o, num_qo_heads, max_n_out, metadata, tail, (hipStream_t)stream, batch.n_seqs);
 }
 
-extern "C" int quest_append_estimate_dyn(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                         uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
-                                         quest_paged_kv_t metadata, const quest_step_state_t* state,
-                                         quest_stream_t stream) {
-    const quest_batch_t one = {1, 0, 0, 0};
-    return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, one, stream, 0);
-}
-
-extern "C" int quest_append_estimate_tiles_dyn(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                               uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
-                                               uint32_t tile_max_offset, quest_paged_kv_t metadata,
-                                               const quest_step_state_t* state, quest_stream_t stream) {
-    if (tile_max_offset == 0) return QUEST_EINVAL;
-    const quest_batch_t one = {1, 0, 0, 0};
-    return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, one, stream,
-                                 tile_max_offset);
-}
-
+// The state-driven append + estimate: whole rows (tile_max_offset 0), or every row of `o` ([n_seqs][num_qo_heads][o_stride])
+// also carries its own tile maxima at `tile_max_offset`.  The grid is sized for the shared capacity; a shorter sequence writes
+// the maxima of its live runs only, and the attention launch masks the tile keys beyond them.
 extern "C" int quest_append_estimate_batched(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
                                              uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
-                                             quest_paged_kv_t metadata, const quest_step_state_t* state,
-                                             quest_batch_t batch, quest_stream_t stream) {
+                                             uint32_t tile_max_offset, quest_paged_kv_t metadata,
+                                             const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream) {
+    if (tile_max_offset) {
+        if (tile_max_offset != ((max_n_out + 7u) & ~7u)) return QUEST_EINVAL;
+        // rows 16-byte aligned: what the attention launch's 8-byte score loads and 4-byte tile-key loads are checked against
+        if (((uintptr_t)o & 15u) != 0 || o_stride % 8u != 0) return QUEST_EINVAL;
+    }
     // every sequence's metadata table must cover the entries the grid is sized for
     if (batch.n_seqs > 1 && (uint64_t)batch.meta_table_stride * metadata.page_size < max_n_out) return QUEST_EINVAL;
-    return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, batch, stream, 0);
+    if (int e = check_dtype_pair(kv, metadata)) return e;
+    if (!k || !v || !state || max_n_out == 0 || o_stride < max_n_out || batch.n_seqs == 0) return QUEST_EINVAL;
+    // the maxima live behind the scores of the same row, readable in 8-byte pieces
+    if (tile_max_offset && o_stride < tile_max_offset + ((((max_n_out + 7u) / 8u) + 3u) & ~3u)) return QUEST_EINVAL;
+    if (int e = check_pool_pair(kv, metadata, true, false)) return e;
+    AppendTail tail = append_tail(k, v, kv, o_stride);
+    tail.state = state;
+    tail.meta_table_stride = batch.meta_table_stride;
+    tail.tile_off = tile_max_offset;
+    return estimate_entry(q, o, num_qo_heads, max_n_out, metadata, tail, (hipStream_t)stream, batch.n_seqs);
 }
 
-// The batched twin of quest_append_estimate_tiles_dyn: every row of `o` ([n_seqs][num_qo_heads][o_stride]) carries its own
-// tile maxima at `tile_max_offset`.  The grid is sized for the shared capacity; a shorter sequence writes the maxima of
-// its live runs only, and the attention launch masks the tile keys beyond them.
-extern "C" int quest_append_estimate_tiles_batched(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                                   uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
-                                                   uint32_t tile_max_offset, quest_paged_kv_t metadata,
-                                                   const quest_step_state_t* state, quest_batch_t batch,
-                                                   quest_stream_t stream) {
-    if (tile_max_offset == 0 || tile_max_offset != ((max_n_out + 7u) & ~7u)) return QUEST_EINVAL;
-    // rows 16-byte aligned: what the attention launch's 8-byte score loads and 4-byte tile-key loads are checked against
-    if (((uintptr_t)o & 15u) != 0 || o_stride % 8u != 0) return QUEST_EINVAL;
-    // every sequence's metadata table must cover the entries the grid is sized for
-    if (batch.n_seqs > 1 && (uint64_t)batch.meta_table_stride * metadata.page_size < max_n_out) return QUEST_EINVAL;
-    return append_estimate_state(k, v, kv, q, o, num_qo_heads, o_stride, max_n_out, metadata, state, batch, stream,
-                                 tile_max_offset);
-}
-
-extern "C" int quest_append_estimate_strided(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                             uint32_t num_qo_heads, uint32_t n_out, uint32_t o_stride,
-                                             quest_paged_kv_t metadata, quest_stream_t stream) {
+extern "C" int quest_append_estimate(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
+                                     uint32_t num_qo_heads, uint32_t n_out, uint32_t o_stride, quest_paged_kv_t metadata,
+                                     quest_stream_t stream) {
     if (int e = check_dtype_pair(kv, metadata)) return e;
     if (!k || !v || (o_stride != 0 && o_stride < n_out)) return QUEST_EINVAL;
     if (int e = check_pool_pair(kv, metadata, false, false)) return e;
     AppendTail tail = append_tail(k, v, kv, o_stride);
     return estimate_entry(q, o, num_qo_heads, n_out, metadata, tail, (hipStream_t)stream, 1);
-}
-
-extern "C" int quest_append_estimate(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
-                                     uint32_t num_qo_heads, uint32_t n_out, quest_paged_kv_t metadata,
-                                     quest_stream_t stream) {
-    return quest_append_estimate_strided(k, v, kv, q, o, num_qo_heads, n_out, 0, metadata, stream);
 }

@@ -250,14 +250,9 @@ __device__ __forceinline__ void estimate_tile(const half_t* __restrict__ q, half
     for (uint32_t t = tid; t < n_scores; t += EWV * kWave) {
         const uint32_t qh = t >> ew_l2, e = e0 + (t & (EW - 1));
         const half_t sc = out_s[t];
-#ifdef QUEST_EST_NOSTORE
-        if (e < n_out && sc == (half_t)12345.f)
-#else
-        if (e < n_out)
-#endif
-        {
-            o[((size_t)o_row0 + (size_t)h0 * G + qh) * tail.o_stride + e] = sc;
-        }
+        // (a build whose score store never fires timed the tile without its writes when the tile shape was chosen, commit
+        // 22528ac: the stores are not what bounds it; no profile file was kept; last in the tree at faef74b)
+        if (e < n_out) o[((size_t)o_row0 + (size_t)h0 * G + qh) * tail.o_stride + e] = sc;
         if (tail.tile_off) {  // launch-uniform: one key per (query head, run of 8 columns): the largest key of the run's valid
                               // scores.  8 consecutive t = 8 consecutive lanes = one run (EW is a multiple of 8): three DPP steps
             int key = e < n_out ? (int)half_key(half_bits(sc)) : 0;

@@ -198,28 +198,18 @@ __device__ __forceinline__ void layer_decode_body(QUEST_LAYER_HEAD_PARAMS, const
     __shared__ uint32_t s_next;
     if (tid == 0) s_next = NW;
     __syncthreads();
-    // Tuning builds (GQA batches in one launch): -DQUEST_LAYER_GQA_STAGGER=<pages> starts the metadata
-    // walk of the j-th query head of a kv-head group j * <pages> metadata pages further (0: a j-th of the row further), so
-    // that the heads of a group -- co-located on one XCD by the grid order -- find each other's metadata in its L2 instead of
-    // streaming it four times; -DQUEST_LAYER_META_CACHED keeps those loads in the L2's normal replacement order.  Measured at
-    // cfg 5: profiles/r06_ab_gqa_one_launch_staggered_walk.txt.  (A page's scores do not depend on when they are computed.)
-#ifdef QUEST_LAYER_GQA_STAGGER
-    const uint32_t walk0 = n_mp == 0 ? 0u : ((hq % group) * (QUEST_LAYER_GQA_STAGGER > 0 ? (uint32_t)QUEST_LAYER_GQA_STAGGER : n_mp / group)) % n_mp;
-#else
-    constexpr uint32_t walk0 = 0;
-#endif
+    // (Starting the walk of the j-th query head of a kv-head group j * 8 / 16 pages or a j-th of the row further, so that a
+    // group's heads find each other's metadata in their XCD's L2, measured slower at cfg 5: 8.25 / 8.36 / 10.05 vs 8.08 us
+    // per sequence-layer -- profiles/r06_ab_gqa_one_launch_staggered_walk.txt; last in the tree at faef74b.)
     auto issue = [&](uint32_t mp, half8 (&mx)[T], half8 (&mn)[T]) {  // request the 16 entries of metadata page mp
         const int32_t pg = ld_uniform_i32(meta_table + mp);
         const half_t* b0 = a_meta + (size_t)pg * p.st.page;
 #pragma unroll
         for (int t = 0; t < T; ++t) {
-#ifdef QUEST_LAYER_META_CACHED
-            mx[t] = ld8(b0 + uni[t] + lane_off);
-            mn[t] = ld8(b0 + uni[t] + lane_off + v_off);
-#else
+            // (streaming loads; keeping them in the L2's normal replacement order measured 8.19 vs 8.08 us per sequence-layer at
+            // cfg 5 -- profiles/r06_ab_gqa_one_launch_staggered_walk.txt; last in the tree at faef74b)
             mx[t] = ld8_stream(b0 + uni[t] + lane_off);
             mn[t] = ld8_stream(b0 + uni[t] + lane_off + v_off);
-#endif
         }
     };
     auto fetch = [&]() -> uint32_t {  // a page from the counter (broadcast from lane 0)
@@ -241,40 +231,20 @@ __device__ __forceinline__ void layer_decode_body(QUEST_LAYER_HEAD_PARAMS, const
         }
     };
     // (Requesting the next page before the current one is scored -- two register sets, 16 loads in flight per lane -- is
-    // SLOWER: 89.9-92.3 vs 86.4 us per launch.  This access shape wants shallow queues: scripts/probe/addr_class_probe.hip.)
-#ifdef QUEST_LAYER_TWO_PAGES
-    // tuning build: TWO metadata pages per round from the counter (16 loads in flight per lane).  Round 5 measured 86.8 vs 86.2 us
-    // on the NHD pool ("this access shape wants shallow queues"); re-measured on the row-rotated pool in round 6:
-    // profiles/r06_ab_layer_kernel_two_pages_per_round.txt
-    for (uint32_t mp = wave; mp < n_mp;) {
-        half8 mx[T], mn[T], mx2[T], mn2[T];
-        issue(mp, mx, mn);
-        const uint32_t mp2 = fetch();
-        const bool has2 = mp2 < n_mp;
-        if (has2) issue(mp2, mx2, mn2);
-        const uint32_t nx = has2 ? fetch() : mp2;
-        if (!ids_parked) {
-            park_ids();
-            ids_parked = true;
-        }
-        score(mp, mx, mn);
-        if (has2) score(mp2, mx2, mn2);
-        mp = nx;
-    }
-#else
+    // SLOWER: 89.9-92.3 vs 86.4 us per launch.  This access shape wants shallow queues: scripts/probe/addr_class_probe.hip.
+    // TWO pages per round from the counter, 16 loads in flight per lane, measured 86.8 vs 86.2 us on the NHD pool and 85.6 vs 84.8
+    // on the row-rotated one -- profiles/r06_ab_layer_kernel_two_pages_per_round.txt; last in the tree at faef74b.)
     for (uint32_t mp = wave; mp < n_mp;) {
         half8 mx[T], mn[T];
-        const uint32_t mpw = mp + walk0 < n_mp ? mp + walk0 : mp + walk0 - n_mp;  // (walk0 = 0 outside the tuning builds)
-        issue(mpw, mx, mn);
+        issue(mp, mx, mn);
         const uint32_t nx = fetch();  // the next round's page, asked for while this round's loads fly
         if (!ids_parked) {
             park_ids();
             ids_parked = true;
         }
-        score(mpw, mx, mn);
+        score(mp, mx, mn);
         mp = nx;
     }
-#endif
     if (!ids_parked) park_ids();  // waves without a round (short sequences)
     QUEST_STAMP(1);
     QUEST_WS_NOW(ws_est)  // this wave's share of the head's pages is scored

@@ -159,7 +159,7 @@ using namespace quest;
 
 static int rope_launch(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads, uint32_t num_kv_heads,
                        uint32_t head_dim, float rcp_scale, float log2_rcp_theta, const float* inv_freq, float attn,
-                       const quest_step_state_t* state, quest_stream_t stream, uint32_t dtype = QUEST_DTYPE_F16) {
+                       const quest_step_state_t* state, quest_stream_t stream, uint32_t dtype) {
     if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!q || !k || num_qo_heads == 0 || num_kv_heads == 0) return QUEST_EINVAL;
     if (n == 0) return 0;
@@ -185,46 +185,8 @@ static int rope_launch(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint3
     return 0;
 }
 
-static int rope_entry(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                      uint32_t head_dim, float rope_scale, float rope_theta, const quest_step_state_t* state,
-                      quest_stream_t stream) {
-    if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
-    return rope_launch(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, 1.0f / rope_scale, -log2f(rope_theta),
-                       nullptr, 1.0f, state, stream);
-}
-
-extern "C" int quest_apply_rope_in_place(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
-                                         uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
-                                         quest_stream_t stream) {
-    return rope_entry(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta, nullptr, stream);
-}
-
-extern "C" int quest_apply_rope_in_place_dyn(void* q, void* k, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                                             uint32_t head_dim, float rope_scale, float rope_theta,
-                                             const quest_step_state_t* state, quest_stream_t stream) {
-    if (!state) return QUEST_EINVAL;
-    return rope_entry(q, k, 1, 0, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta, state, stream);
-}
-
-extern "C" int quest_apply_rope_in_place_batched(void* q, void* k, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                                                 uint32_t head_dim, float rope_scale, float rope_theta,
-                                                 const quest_step_state_t* state, quest_batch_t batch,
-                                                 quest_stream_t stream) {
-    if (!state || batch.n_seqs == 0) return QUEST_EINVAL;
-    return rope_entry(q, k, batch.n_seqs, 0, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta, state, stream);
-}
-
-extern "C" int quest_apply_rope_in_place_freqs(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
-                                               uint32_t num_kv_heads, uint32_t head_dim, const float* inv_freq,
-                                               float attention_factor, const quest_step_state_t* states,
-                                               quest_stream_t stream) {
-    if (bad_rope_table(inv_freq, attention_factor)) return QUEST_EINVAL;
-    return rope_launch(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, 1.0f, 0.f, inv_freq, attention_factor,
-                       states, stream);
-}
-
 // The two operators that come with neither a pool view nor a handler get ONE typed entry each (the element type as an
-// argument); the existing entries keep their signatures and mean fp16.
+// argument); the entries with the reference's argument lists mean fp16.
 extern "C" int quest_apply_rope_in_place_dtype(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
                                                uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
                                                const float* inv_freq, float attention_factor,
@@ -238,6 +200,13 @@ extern "C" int quest_apply_rope_in_place_dtype(void* q, void* k, uint32_t n, uin
     if (rope_scale == 0.f || rope_theta <= 0.f) return QUEST_EINVAL;
     return rope_launch(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, 1.0f / rope_scale, -log2f(rope_theta),
                        nullptr, 1.0f, states, stream, dtype);
+}
+
+extern "C" int quest_apply_rope_in_place(void* q, void* k, uint32_t n, uint32_t past_kv_len, uint32_t num_qo_heads,
+                                         uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
+                                         quest_stream_t stream) {
+    return quest_apply_rope_in_place_dtype(q, k, n, past_kv_len, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta,
+                                           nullptr, 1.0f, nullptr, QUEST_DTYPE_F16, stream);
 }
 
 // Per-head q/k RMSNorm + RoPE in place (qk_norm_rope_kernel): the rows and the position sources of

@@ -64,10 +64,9 @@ static StepAdvance take_armed_advance(quest_decode_handler* h) {
 // behind this layer's kernels, as its own launch
 static int flush_armed_advance(quest_decode_handler* h, hipStream_t s) {
     if (!h->armed_advance.st) return 0;
-    const StepAdvance a = take_armed_advance(h);
-    if (a.batch.n_seqs == 1)  // (one sequence: its tables are plain arrays, no strides to check)
-        return quest_step_state_advance(a.st, a.kv_table, a.meta_table, a.page_size, a.max_kv_pages, a.max_meta_pages,
-                                        (quest_stream_t)s);
+    StepAdvance a = take_armed_advance(h);
+    if (a.batch.n_seqs == 1)  // (one sequence: its tables are plain arrays whose strides nobody reads; the entry checks them)
+        a.batch.kv_table_stride = a.max_kv_pages, a.batch.meta_table_stride = a.max_meta_pages;
     return quest_step_state_advance_batched(a.st, a.kv_table, a.meta_table, a.page_size, a.max_kv_pages, a.max_meta_pages,
                                             a.batch, (quest_stream_t)s);
 }
@@ -665,12 +664,6 @@ extern "C" int quest_decode_forward_shared_batched(quest_decode_handler_t* h, co
     return shared_entry(h, r, (hipStream_t)stream);
 }
 
-extern "C" int quest_decode_forward_shared_dyn(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
-                                               uint32_t num_qo_heads, const quest_step_state_t* state, float* lse,
-                                               quest_stream_t stream) {
-    return quest_decode_forward_shared_batched(h, q, o, kv, num_qo_heads, state, {1, 0, 0, 0}, lse, stream);
-}
-
 extern "C" int quest_decode_append_forward_shared_batched(quest_decode_handler_t* h, const void* k, const void* v,
                                                           quest_paged_kv_t metadata, const void* q, void* o,
                                                           quest_paged_kv_t kv, uint32_t num_qo_heads,
@@ -684,17 +677,10 @@ extern "C" int quest_decode_append_forward_shared_batched(quest_decode_handler_t
     return shared_entry(h, r, (hipStream_t)stream);
 }
 
-extern "C" int quest_decode_append_forward_shared_dyn(quest_decode_handler_t* h, const void* k, const void* v,
-                                                      quest_paged_kv_t metadata, const void* q, void* o, quest_paged_kv_t kv,
-                                                      uint32_t num_qo_heads, const quest_step_state_t* state, float* lse,
-                                                      quest_stream_t stream) {
-    return quest_decode_append_forward_shared_batched(h, k, v, metadata, q, o, kv, num_qo_heads, state, {1, 0, 0, 0}, lse, stream);
-}
-
-extern "C" int quest_decode_forward_fused_topk_strided(quest_decode_handler_t* h, const void* q, void* o,
-                                                       quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
-                                                       uint32_t n_scores, uint32_t score_stride, void* topk_val_out,
-                                                       int32_t* topk_idx_out, float* lse, quest_stream_t stream) {
+extern "C" int quest_decode_forward_fused_topk(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
+                                               uint32_t num_qo_heads, const void* scores, uint32_t n_scores,
+                                               uint32_t score_stride, void* topk_val_out, int32_t* topk_idx_out, float* lse,
+                                               quest_stream_t stream) {
     if (!scores || (score_stride != 0 && score_stride < n_scores)) return QUEST_EINVAL;
     DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
     r.scores = scores, r.n_scores = n_scores, r.score_stride = score_stride;
@@ -702,61 +688,20 @@ extern "C" int quest_decode_forward_fused_topk_strided(quest_decode_handler_t* h
     return decode_entry(h, r, (hipStream_t)stream);
 }
 
-extern "C" int quest_decode_forward_fused_topk(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
-                                               uint32_t num_qo_heads, const void* scores, uint32_t n_scores,
-                                               void* topk_val_out, int32_t* topk_idx_out, float* lse,
-                                               quest_stream_t stream) {
-    return quest_decode_forward_fused_topk_strided(h, q, o, kv, num_qo_heads, scores, n_scores, 0, topk_val_out,
-                                                   topk_idx_out, lse, stream);
-}
-
-// The state-driven fused launches: whole rows (tile_max_offset 0) or rows that carry their tile maxima at
+// The state-driven fused launch: whole rows (tile_max_offset 0) or rows that carry their tile maxima at
 // `tile_max_offset`, one sequence or a batch (blockIdx.z = sequence; live lengths and budgets per sequence).  Dispatch
 // (keys per thread) is chosen for the longest row the graph will see.
-static int fused_topk_state(quest_decode_handler* h, DecodeRequest r, const void* scores, uint32_t score_stride,
-                            uint32_t max_n_scores, uint32_t tile_max_offset, hipStream_t s) {
-    if (!scores || !r.state || score_stride < max_n_scores) return QUEST_EINVAL;
-    if (r.batch.n_seqs > 1 && r.batch.kv_table_stride < max_n_scores + 1) return QUEST_EINVAL;
-    r.scores = scores, r.n_scores = max_n_scores, r.score_stride = score_stride, r.tile_off = tile_max_offset;
-    return decode_entry(h, r, s);
-}
-
 extern "C" int quest_decode_forward_fused_topk_batched(quest_decode_handler_t* h, const void* q, void* o,
                                                        quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
                                                        uint32_t score_stride, uint32_t max_n_scores,
-                                                       const quest_step_state_t* state, quest_batch_t batch, float* lse,
-                                                       quest_stream_t stream) {
+                                                       uint32_t tile_max_offset, const quest_step_state_t* state,
+                                                       quest_batch_t batch, float* lse, quest_stream_t stream) {
+    if (!scores || !state || score_stride < max_n_scores) return QUEST_EINVAL;
+    if (batch.n_seqs > 1 && batch.kv_table_stride < max_n_scores + 1) return QUEST_EINVAL;
     DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
     r.state = state, r.batch = batch;
-    return fused_topk_state(h, r, scores, score_stride, max_n_scores, 0, (hipStream_t)stream);
-}
-
-extern "C" int quest_decode_forward_fused_topk_dyn(quest_decode_handler_t* h, const void* q, void* o,
-                                                   quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
-                                                   uint32_t score_stride, uint32_t max_n_scores,
-                                                   const quest_step_state_t* state, float* lse, quest_stream_t stream) {
-    return quest_decode_forward_fused_topk_batched(h, q, o, kv, num_qo_heads, scores, score_stride, max_n_scores, state,
-                                                   {1, 0, 0, 0}, lse, stream);
-}
-
-extern "C" int quest_decode_forward_fused_topk_tiles_batched(quest_decode_handler_t* h, const void* q, void* o,
-                                                             quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
-                                                             uint32_t score_stride, uint32_t max_n_scores,
-                                                             uint32_t tile_max_offset, const quest_step_state_t* state,
-                                                             quest_batch_t batch, float* lse, quest_stream_t stream) {
-    if (!scores || !state || score_stride < max_n_scores || tile_max_offset == 0) return QUEST_EINVAL;
-    DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
-    r.state = state, r.batch = batch;
-    return fused_topk_state(h, r, scores, score_stride, max_n_scores, tile_max_offset, (hipStream_t)stream);
-}
-
-extern "C" int quest_decode_forward_fused_topk_tiles_dyn(quest_decode_handler_t* h, const void* q, void* o,
-                                                         quest_paged_kv_t kv, uint32_t num_qo_heads, const void* scores,
-                                                         uint32_t score_stride, uint32_t max_n_scores,
-                                                         uint32_t tile_max_offset, const quest_step_state_t* state, float* lse,
-                                                         quest_stream_t stream) {
-    return quest_decode_forward_fused_topk_tiles_batched(h, q, o, kv, num_qo_heads, scores, score_stride, max_n_scores,
-                                                         tile_max_offset, state, {1, 0, 0, 0}, lse, stream);
+    r.scores = scores, r.n_scores = max_n_scores, r.score_stride = score_stride, r.tile_off = tile_max_offset;
+    return decode_entry(h, r, (hipStream_t)stream);
 }
 
 // append + estimate + top-k + sparse attention of one layer for a whole batch in ONE launch (layer_device.cuh).

@@ -125,10 +125,9 @@ __global__ __launch_bounds__(kTkThreads) void topk_batched_kernel(const uint16_t
 
 using namespace quest;
 
-extern "C" int quest_topk_filtering_strided(const void* estimated_value, uint32_t value_stride,
-                                            const int32_t* estimated_indices, void* d_out, int32_t* indices_out, void* buf,
-                                            uint32_t num_heads, uint32_t num_pages, uint32_t page_budget,
-                                            quest_stream_t stream) {
+extern "C" int quest_topk_filtering(const void* estimated_value, uint32_t value_stride, const int32_t* estimated_indices,
+                                    void* d_out, int32_t* indices_out, void* buf, uint32_t num_heads, uint32_t num_pages,
+                                    uint32_t page_budget, quest_stream_t stream) {
     (void)buf;
     if (!estimated_value || !estimated_indices) return QUEST_EINVAL;
     if (num_heads == 0 || num_pages == 0) return QUEST_EINVAL;
@@ -156,13 +155,6 @@ extern "C" int quest_topk_filtering_strided(const void* estimated_value, uint32_
 #undef QUEST_TOPK_LAUNCH
     QUEST_LAUNCH_CHECK();
     return 0;
-}
-
-extern "C" int quest_topk_filtering(const void* estimated_value, const int32_t* estimated_indices, void* d_out,
-                                    int32_t* indices_out, void* buf, uint32_t num_heads, uint32_t num_pages,
-                                    uint32_t page_budget, quest_stream_t stream) {
-    return quest_topk_filtering_strided(estimated_value, 0, estimated_indices, d_out, indices_out, buf, num_heads, num_pages,
-                                        page_budget, stream);
 }
 
 extern "C" int quest_topk_filtering_batched(const void* scores, uint32_t score_stride, uint32_t max_num_pages,

@@ -148,14 +148,9 @@ __device__ __forceinline__ uint32_t lowest_bits(uint32_t x, uint32_t keep) {
 // Selection proper.  n = live row length (<= n_cap), k = pages to select (<= n).  Writes the physical page of every
 // output slot in [slot_begin, slot_end) to s_sel[slot - slot_begin]; the caller's next barrier publishes them.
 // bm: two bitmaps of kBmWords words.  ids_s: LDS copy of the page table (filled here) or nullptr (read from `table`).
-// SOLO: the two scans (threshold over the histogram, ranks over the bitmaps) are done by wave 0 alone and published
-// through LDS (one more barrier) instead of by every wave redundantly.
-#ifdef QUEST_FE2_SOLO
-constexpr bool kFe2Solo = true;
-#else
-constexpr bool kFe2Solo = false;
-#endif
-
+// The two scans (threshold over the histogram, ranks over the bitmaps) are done by every wave for itself.  (Wave 0 alone,
+// publishing through LDS behind one more barrier, measured 13.4 vs 13.6 us at cfg 3 but 22.9 vs 21.5 at cfg 4, the rows this
+// front end serves -- docs/history/r2.md; counters: profiles/r02_sq_counters_cfg3.json; last in the tree at faef74b.)
 template <int NT, int FC>
 __device__ __forceinline__ void fe2_select(TopkSmem<NT>& sm, uint32_t (&bm)[2][kBmWords],
                                            const Fe2Raw<fe2_has_ids(FC)> (&raw)[FC / 4],
@@ -259,44 +254,33 @@ __device__ __forceinline__ void fe2_select(TopkSmem<NT>& sm, uint32_t (&bm)[2][k
     uint32_t T, need;
     {
         uint32_t thr_bin = 0, above = 0;
-        if (!kFe2Solo || wave == 0) {
-            // Only the bins [0, nb) can hold keys (nb = the row's key range in bins; with the pre-filter the range starts
-            // at the lower bound of the threshold and is a few hundred bins, not 2048): the lanes share THOSE bins, top
-            // down -- lane l owns the bpl bins below top - bpl l, bpl = ceil(nb / 64) <= 32 -- so the loop runs bpl times
-            // instead of 32 (round 4: the threshold phase of a cfg-4 workgroup was 0.96 us of 32 LDS reads per lane).
-            // Reads are rotated by the lane number so that the lanes of a read group hit different banks.
-            const uint32_t nb = (range >> shift) + 1u;                 // <= kBins1
-            const uint32_t bpl = (nb + 63u) >> 6;                      // wave-uniform, 1 .. 32
-            const uint32_t top = bpl << 6;                             // bins [nb, top) are empty (cleared), top <= kBins1
-            const uint32_t base = top - bpl * (lane + 1u);
-            const uint32_t rot = lane % bpl;                           // (one division per thread, outside the loop)
-            uint32_t tot = 0;
-            for (uint32_t j = 0; j < bpl; ++j) {
-                uint32_t jj = j + rot;
-                jj = jj >= bpl ? jj - bpl : jj;
-                tot += sm.hist1[base + jj];
-            }
-            const uint32_t incl = wave_scan_incl_dpp(tot);
-            const unsigned long long m1 = __ballot(incl >= k);
-            const uint32_t L = (uint32_t)__builtin_ctzll(m1);  // m1 != 0: the row holds n >= k keys
-            const uint32_t above_l = (uint32_t)__builtin_amdgcn_readlane((int)(incl - tot), (int)L);
-            const uint32_t base_l = top - bpl * (L + 1u);
-            const uint32_t c = lane < bpl ? sm.hist1[base_l + bpl - 1u - lane] : 0u;  // bins of lane L, descending
-            const uint32_t incl2 = wave_scan_incl_dpp(c);
-            const unsigned long long m2 = __ballot(lane < bpl && above_l + incl2 >= k);
-            const uint32_t I = (uint32_t)__builtin_ctzll(m2);
-            thr_bin = base_l + bpl - 1u - I;
-            above = above_l + (uint32_t)__builtin_amdgcn_readlane((int)(incl2 - c), (int)I);
-            if (kFe2Solo && lane == 0) {
-                sm.misc[0] = thr_bin;
-                sm.misc[1] = above;
-            }
+        // Only the bins [0, nb) can hold keys (nb = the row's key range in bins; with the pre-filter the range starts
+        // at the lower bound of the threshold and is a few hundred bins, not 2048): the lanes share THOSE bins, top
+        // down -- lane l owns the bpl bins below top - bpl l, bpl = ceil(nb / 64) <= 32 -- so the loop runs bpl times
+        // instead of 32 (round 4: the threshold phase of a cfg-4 workgroup was 0.96 us of 32 LDS reads per lane).
+        // Reads are rotated by the lane number so that the lanes of a read group hit different banks.
+        const uint32_t nb = (range >> shift) + 1u;                 // <= kBins1
+        const uint32_t bpl = (nb + 63u) >> 6;                      // wave-uniform, 1 .. 32
+        const uint32_t top = bpl << 6;                             // bins [nb, top) are empty (cleared), top <= kBins1
+        const uint32_t base = top - bpl * (lane + 1u);
+        const uint32_t rot = lane % bpl;                           // (one division per thread, outside the loop)
+        uint32_t tot = 0;
+        for (uint32_t j = 0; j < bpl; ++j) {
+            uint32_t jj = j + rot;
+            jj = jj >= bpl ? jj - bpl : jj;
+            tot += sm.hist1[base + jj];
         }
-        if (kFe2Solo) {
-            __syncthreads();  // C: threshold bin published
-            thr_bin = sm.misc[0];
-            above = sm.misc[1];
-        }
+        const uint32_t incl = wave_scan_incl_dpp(tot);
+        const unsigned long long m1 = __ballot(incl >= k);
+        const uint32_t L = (uint32_t)__builtin_ctzll(m1);  // m1 != 0: the row holds n >= k keys
+        const uint32_t above_l = (uint32_t)__builtin_amdgcn_readlane((int)(incl - tot), (int)L);
+        const uint32_t base_l = top - bpl * (L + 1u);
+        const uint32_t c = lane < bpl ? sm.hist1[base_l + bpl - 1u - lane] : 0u;  // bins of lane L, descending
+        const uint32_t incl2 = wave_scan_incl_dpp(c);
+        const unsigned long long m2 = __ballot(lane < bpl && above_l + incl2 >= k);
+        const uint32_t I = (uint32_t)__builtin_ctzll(m2);
+        thr_bin = base_l + bpl - 1u - I;
+        above = above_l + (uint32_t)__builtin_amdgcn_readlane((int)(incl2 - c), (int)I);
         if (shift == 0) {  // a bin IS a key value (the usual case: one or two binades of fp16 scores)
             T = kmin + thr_bin;
             need = k - above;
@@ -349,8 +333,7 @@ __device__ __forceinline__ void fe2_select(TopkSmem<NT>& sm, uint32_t (&bm)[2][k
     QUEST_SUBSTAMP(6);
 
     // ---- ranks: a wave scans the whole bitmap (a few words per lane) and extracts the slots of this workgroup's
-    // chunk from the lanes it is responsible for (redundant form: lane % waves == wave; solo form: wave 0, all lanes)
-    if (kFe2Solo && wave != 0) return;
+    // chunk from the lanes it is responsible for (lane % waves == wave)
     const uint32_t W = (n + lead + 31u) >> 5, wpl = (W + 63u) >> 6;  // words per lane, <= 8
     uint32_t sel[8], eqc = 0;
     uint32_t eqw[8];
@@ -378,7 +361,7 @@ __device__ __forceinline__ void fe2_select(TopkSmem<NT>& sm, uint32_t (&bm)[2][k
         }
     uint32_t rank = wave_scan_incl_dpp(cnt) - cnt;  // output slot of this lane's first selected column
     QUEST_SUBSTAMP(7);
-    if ((kFe2Solo || (lane % NWV) == wave) && rank < slot_end && rank + cnt > slot_begin) {
+    if ((lane % NWV) == wave && rank < slot_end && rank + cnt > slot_begin) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             if ((uint32_t)j >= wpl) break;

@@ -30,7 +30,7 @@ a.mode, a.layers = "graph-static", 4
 dev = torch.device("cuda", 0)
 w = bench.Workload(a, dev)
 from quest_amd import _kernels  # noqa: E402
-from quest_amd._lib import lib, check  # noqa: E402
+from quest_amd._lib import Batch, check, lib  # noqa: E402
 
 qu, ctl = w.qu, w.ctl
 ctl.set_page_budget(w.page_budget)
@@ -61,15 +61,16 @@ for fused in variants:
             o = torch.empty_like(q)
             if fused == "dyn":
                 kv = _kernels._paged(c2.kv_cache.buf_layer(l), c2.kv_table_full, None, 1, 0, c2.layout)
-                check(lib.quest_decode_forward_fused_topk_dyn(h2._wrapper._h, w2.q[l].data_ptr(), o.data_ptr(), kv, q.size(1),
-                                                              sc2[l].data_ptr(), sc2[l].size(1), c2.max_pages - 1,
-                                                              c2.step_state.data_ptr(), lse.data_ptr(),
-                                                              torch.cuda.current_stream().cuda_stream), "dyn")
+                check(lib.quest_decode_forward_fused_topk_batched(h2._wrapper._h, w2.q[l].data_ptr(), o.data_ptr(), kv, q.size(1),
+                                                                  sc2[l].data_ptr(), sc2[l].size(1), c2.max_pages - 1, 0,
+                                                                  c2.step_state.data_ptr(), Batch(1, 0, 0, 0, None),
+                                                                  lse.data_ptr(), torch.cuda.current_stream().cuda_stream),
+                      "dyn")
             elif fused:
                 kv = _kernels._paged(ctl.kv_cache.buf_layer(l), ctl.kv_indices_with_last, None, ctl.kv_cache.last_page_len,
                                      ctl.kv_last_page_idx, ctl.layout)
                 check(lib.quest_decode_forward_fused_topk(h._wrapper._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), est[l].data_ptr(),
-                                                          est[l].size(1), None, None, lse.data_ptr(),
+                                                          est[l].size(1), 0, None, None, lse.data_ptr(),
                                                           torch.cuda.current_stream().cuda_stream), "fused")
             else:
                 qu.decode_topk(est[l], ctl)

@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from test_return_codes import EINVAL, EUNSUPPORTED, PLAN, _device_visible, _entries, _kv
+from test_return_codes import _call as _entry_call
 
 F16, BF16 = 0, 1
 
@@ -24,11 +25,11 @@ def _handler(lib, dtype=F16):
 
 
 def _call(lib, name, h, **rep):
-    args = dict(_entries()[name])
-    args.update(rep)
+    """`name`: an entry in one of its forms, as tests/test_return_codes.py lists them."""
+    entry, args = _entry_call(_entries(), name, rep)
     if "h" in args:
         args["h"] = h
-    return getattr(lib, name)(*args.values())
+    return getattr(lib, entry)(*args.values())
 
 
 def test_unknown_dtype_is_einval_before_any_launch():
@@ -82,7 +83,7 @@ def test_mismatched_views_and_handlers_are_einval_before_any_launch():
                 views = {p: _kv(dtype=BF16) for p in ("kv", "metadata") if p in dict(_entries()[name])}
                 assert _call(lib, name, hbf, **views) > 0, name
             for name in ("quest_append_kv_cache_decode", "quest_append_kv_cache_prefill", "quest_estimate_attn_score",
-                         "quest_append_estimate"):
+                         "quest_append_estimate, contiguous rows"):
                 views = {p: _kv(dtype=BF16) for p in ("kv", "metadata") if p in dict(_entries()[name])}
                 assert _call(lib, name, None, **views) > 0, name
     finally:

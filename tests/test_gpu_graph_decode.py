@@ -564,14 +564,15 @@ def test_next_tokens_reservation_riding_in_the_last_launch_equals_the_advance_la
 
 @pytest.mark.parametrize("Hq,Hkv,D,layout", [(8, 2, 128, 0)])
 def test_single_sequence_c_entries_equal_the_python_path(Hq, Hkv, D, layout):
-    """The package runs a single sequence as a batch of one through the ``_batched`` C entries; the exported ``_dyn``
-    entries (the same internal functions at ``n_seqs == 1``) stay for C callers.  Two controllers over identical pools, one
-    stepped by ``quest_amd.utils``, one by the ``_dyn`` entries called through ``quest_amd._lib.lib`` -- step advance, RoPE,
-    dense + append, append, dense, append + estimate and fused top-k (whole row and tiles) -- token after token across
-    KV-page and metadata-page boundaries: step states, page scores, outputs and pool pages identical bit for bit."""
+    """A single sequence is a batch of one, for the package and for a C caller alike.  Two controllers over identical pools,
+    one stepped by ``quest_amd.utils`` (one-row views of its state and tables), one by the ``_batched`` entries called through
+    ``quest_amd._lib.lib`` with an explicit ``quest_batch_t{1, 0, 0, 0, NULL}`` and the sequence's plain arrays -- step
+    advance, RoPE, dense + append, append, dense, append + estimate and fused top-k (whole row and tiles) -- token after
+    token across KV-page and metadata-page boundaries: step states, page scores, outputs and pool pages identical bit for
+    bit."""
     import quest_amd.utils as qu
     from quest_amd import _kernels
-    from quest_amd._lib import check, lib
+    from quest_amd._lib import Batch, check, lib
 
     dev = torch.device("cuda:0")
     layers, B, steps = 4, 20, 45
@@ -609,28 +610,33 @@ def test_single_sequence_c_entries_equal_the_python_path(Hq, Hkv, D, layout):
         st, kvt, mt, s = ctl.step_state.data_ptr(), ctl.kv_table_full, ctl.meta_table_full, _kernels._stream(v)
         sparse, dense = ctl._decode_handler._wrapper._h, ctl._dense_handler._wrapper._h
         max_n, off = ctl.max_pages - 1, _kernels.tile_max_offset(ctl.max_pages - 1)
-        check(lib.quest_step_state_advance(st, kvt.data_ptr(), mt.data_ptr(), PAGE, kvt.numel(), mt.numel(), s), "advance")
+        one = Batch(1, 0, 0, 0, None)
+        # (the step advance checks the table strides against the capacities whatever n_seqs is)
+        check(lib.quest_step_state_advance_batched(st, kvt.data_ptr(), mt.data_ptr(), PAGE, kvt.numel(), mt.numel(),
+                                                   Batch(1, kvt.numel(), mt.numel(), 0, None), s), "advance")
         outs = [torch.empty_like(q[l]) for l in range(layers)]
         for l in range(layers):
-            check(lib.quest_apply_rope_in_place_dyn(q[l].data_ptr(), k[l].data_ptr(), Hq, Hkv, D, 1.0, 1e4, st, s), "rope")
+            check(lib.quest_apply_rope_in_place_dtype(q[l].data_ptr(), k[l].data_ptr(), 1, 0, Hq, Hkv, D, 1.0, 1e4, None, 1.0,
+                                                      st, 0, s), "rope")
             kv = _kernels._paged(ctl.kv_cache.buf_layer(l), kvt, None, 1, 0, ctl.layout)
             meta = _kernels._paged(ctl.metadata_cache.buf_layer(l), mt, None, 1, 0, ctl.layout)
             qp, kp, vp, op = q[l].data_ptr(), k[l].data_ptr(), v.data_ptr(), outs[l].data_ptr()
             if l == 0:
-                check(lib.quest_decode_append_forward_shared_dyn(dense, kp, vp, meta, qp, op, kv, Hq, st, None, s), "dense")
+                check(lib.quest_decode_append_forward_shared_batched(dense, kp, vp, meta, qp, op, kv, Hq, st, one, None, s),
+                      "dense")
             elif l == 1:
-                check(lib.quest_append_kv_cache_decode_dyn(kp, vp, kv, meta, st, s), "append")
-                check(lib.quest_decode_forward_shared_dyn(dense, qp, op, kv, Hq, st, None, s), "dense")
+                check(lib.quest_append_kv_cache_decode_batched(kp, vp, kv, meta, st, one, s), "append")
+                check(lib.quest_decode_forward_shared_batched(dense, qp, op, kv, Hq, st, one, None, s), "dense")
             elif l == 2:
-                check(lib.quest_append_estimate_dyn(kp, vp, kv, qp, sc_row.data_ptr(), Hq, sc_row.size(1), max_n, meta, st, s),
-                      "estimate")
-                check(lib.quest_decode_forward_fused_topk_dyn(sparse, qp, op, kv, Hq, sc_row.data_ptr(), sc_row.size(1),
-                                                              max_n, st, None, s), "top-k")
+                check(lib.quest_append_estimate_batched(kp, vp, kv, qp, sc_row.data_ptr(), Hq, sc_row.size(1), max_n, 0, meta,
+                                                        st, one, s), "estimate")
+                check(lib.quest_decode_forward_fused_topk_batched(sparse, qp, op, kv, Hq, sc_row.data_ptr(), sc_row.size(1),
+                                                                  max_n, 0, st, one, None, s), "top-k")
             else:
-                check(lib.quest_append_estimate_tiles_dyn(kp, vp, kv, qp, sc_tiles.data_ptr(), Hq, sc_tiles.size(1), max_n,
-                                                          off, meta, st, s), "estimate (tiles)")
-                check(lib.quest_decode_forward_fused_topk_tiles_dyn(sparse, qp, op, kv, Hq, sc_tiles.data_ptr(),
-                                                                    sc_tiles.size(1), max_n, off, st, None, s),
+                check(lib.quest_append_estimate_batched(kp, vp, kv, qp, sc_tiles.data_ptr(), Hq, sc_tiles.size(1), max_n, off,
+                                                        meta, st, one, s), "estimate (tiles)")
+                check(lib.quest_decode_forward_fused_topk_batched(sparse, qp, op, kv, Hq, sc_tiles.data_ptr(),
+                                                                  sc_tiles.size(1), max_n, off, st, one, None, s),
                       "top-k (tiles)")
         return outs
 

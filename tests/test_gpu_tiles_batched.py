@@ -1,4 +1,4 @@
-"""The tiles launches for a BATCH (quest_append_estimate_tiles_batched + quest_decode_forward_fused_topk_tiles_batched:
+"""The tiles launches for a BATCH (quest_append_estimate_batched + quest_decode_forward_fused_topk_batched with tile_max_offset != 0:
 every row of the batched score scratch carries its own per-8-page maxima, csrc/decode_device.cuh sparse_decode_tiles_body
 with blockIdx.z = sequence):
 

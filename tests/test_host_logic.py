@@ -20,6 +20,15 @@ def test_library_exports_every_declared_symbol():
     assert declared == set(_lib.SIGNATURES), (declared ^ set(_lib.SIGNATURES))
     for name in declared:
         assert hasattr(_lib.lib, name)
+    # ... and nothing else: no quest_* function in the dynamic symbol table that the header does not declare
+    import subprocess
+
+    readelf = os.path.join(os.environ.get("ROCM_LLVM_BIN", "/opt/rocm/lib/llvm/bin"), "llvm-readelf")
+    table = subprocess.check_output([readelf, "--dyn-syms", "-W", _lib.LIB_PATH], text=True).split("\n")
+    # Num: Value Size Type Bind Vis Ndx Name
+    exported = {f[7] for f in (ln.split() for ln in table)
+                if len(f) == 8 and f[3] == "FUNC" and f[6] != "UND" and f[7].startswith("quest_")}
+    assert exported == declared, (exported ^ declared)
     assert b"gfx950" in _lib.lib.quest_build_info()
     assert b"begin_forward" in _lib.lib.quest_error_string(-3)
 
@@ -67,7 +76,7 @@ def test_c_abi_argument_errors_without_gpu():
     empty = PagedKV()
     assert lib.quest_append_kv_cache_decode(None, None, empty, empty, None) == -1
     assert lib.quest_estimate_attn_score(None, None, 32, 10, empty, None) == -1
-    assert lib.quest_topk_filtering(None, None, None, None, None, 32, 10, 5, None) == -1
+    assert lib.quest_topk_filtering(None, 0, None, None, None, None, 32, 10, 5, None) == -1
     h = ctypes.c_void_p()
     assert lib.quest_decode_handler_create(ctypes.byref(h), 7) == -1
     assert lib.quest_decode_handler_create(ctypes.byref(h), 0) == 0
@@ -396,20 +405,18 @@ def test_round3_entry_points_validate_arguments_without_gpu():
     b2 = Batch(2, 4, 0, 0, None)
     assert lib.quest_topk_filtering_batched(one, 16, 8, one, one, one, 4, 32, 5, one, b2, None) == -1  # table stride < pages
     assert lib.quest_decode_forward_batched(None, one, one, empty, 32, one, 4, one, b1, None, None) == -1
-    assert lib.quest_append_estimate_strided(None, None, empty, one, one, 32, 10, 16, empty, None) == -1
+    assert lib.quest_append_estimate(None, None, empty, one, one, 32, 10, 16, empty, None) == -1
     kv = PagedKV(data=16, indices=16, indptr=16, num_heads=32, page_size=16, head_dim=128, page_budget=0,
                  last_page_len=1, last_page_idx=0, layout=0)
-    assert lib.quest_append_estimate_strided(one, one, kv, one, one, 32, 10, 4, kv, None) == -1     # o_stride < n_out
+    assert lib.quest_append_estimate(one, one, kv, one, one, 32, 10, 4, kv, None) == -1     # o_stride < n_out
     h = ctypes.c_void_p()
     assert lib.quest_decode_handler_create(ctypes.byref(h), 0) == 0
-    assert lib.quest_decode_forward_fused_topk_strided(h, one, one, kv, 32, one, 10, 4, None, None, None, None) == -1
-    assert lib.quest_decode_forward_fused_topk_strided(h, one, one, kv, 32, None, 10, 16, None, None, None, None) == -1
+    assert lib.quest_decode_forward_fused_topk(h, one, one, kv, 32, one, 10, 4, None, None, None, None) == -1
+    assert lib.quest_decode_forward_fused_topk(h, one, one, kv, 32, None, 10, 16, None, None, None, None) == -1
     assert lib.quest_decode_set_front_end(h, 3) == 0 and lib.quest_decode_set_front_end(h, 4) == -1  # (4-6: removed in round 5)
     assert lib.quest_decode_set_front_end(h, 0) == 0
     # round-5 entries: the tiles launches and the one-launch layer refuse malformed arguments before anything runs
-    assert lib.quest_append_estimate_tiles_dyn(one, one, kv, one, one, 32, 16, 10, 0, kv, one, None) == -1   # no offset
-    assert lib.quest_append_estimate_tiles_dyn(one, one, kv, one, one, 32, 16, 10, 16, kv, one, None) == -1  # stride has no room
-    assert lib.quest_decode_forward_fused_topk_tiles_dyn(h, one, one, kv, 32, one, 32, 10, 0, one, None, None) == -1
+    assert lib.quest_append_estimate_batched(one, one, kv, one, one, 32, 16, 10, 16, kv, one, b1, None) == -1  # no room for maxima
     assert lib.quest_decode_layer_fused_batched(h, None, one, kv, one, one, kv, 32, 10, one, b1, None, 0, None, None) == -1
     assert lib.quest_decode_layer_fused_batched(h, one, one, kv, one, one, kv, 32, 10, one, b1, None, 0, None, None) == -3  # no plan
     # the prefill kernel's entry: null tensors, no pages, more query rows than cached tokens, a group that does not divide,
@@ -431,8 +438,10 @@ def test_round3_entry_points_validate_arguments_without_gpu():
     assert lib.quest_decode_norm_gemv(one, None, 0.0, one, one, 60, 8, None) == -2          # in_dim % 8
     assert lib.quest_decode_gemv_residual(one, one, None, 64, 8, None) == -1
     assert lib.quest_decode_mlp_gate_up(one, None, 1e-5, one, one, one, 64, 128, None) == -1  # the MLP launch needs gamma
-    assert lib.quest_decode_qkv_rope(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 1.0, 1e4, None, None) == -1
-    assert lib.quest_decode_qkv_rope(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 0.0, 1e4, one, None) == -1
+    assert lib.quest_decode_qkv_rope(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 1.0, 1e4, None, 1.0, None,
+                                     None) == -1
+    assert lib.quest_decode_qkv_rope(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 0.0, 1e4, None, 1.0, one,
+                                     None) == -1
     # ... and their n-token forms: 1..16 tokens, same argument rules (checked before anything is launched)
     assert lib.quest_decode_norm_gemv_batched(None, None, 0.0, one, one, 64, 8, 8, None) == -1
     assert lib.quest_decode_norm_gemv_batched(one, None, 0.0, one, one, 64, 8, 0, None) == -1
@@ -440,9 +449,9 @@ def test_round3_entry_points_validate_arguments_without_gpu():
     assert lib.quest_decode_norm_gemv_batched(one, None, 0.0, one, one, 60, 8, 8, None) == -2   # in_dim % 8
     assert lib.quest_decode_gemv_residual_batched(one, one, None, 64, 8, 8, None) == -1
     assert lib.quest_decode_mlp_gate_up_batched(one, None, 1e-5, one, one, one, 64, 128, 8, None) == -1
-    assert lib.quest_decode_qkv_rope_batched(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 1.0, 1e4, None, 8,
+    assert lib.quest_decode_qkv_rope_batched(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 1.0, 1e4, None, 1.0, None, 8,
                                              None) == -1
-    assert lib.quest_decode_qkv_rope_batched(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 72, 1.0, 1e4, one, 8,
+    assert lib.quest_decode_qkv_rope_batched(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 72, 1.0, 1e4, None, 1.0, one, 8,
                                              None) == -2   # head_dim % 16
     assert lib.quest_build_info().startswith(b"quest_hip gfx950 src=")
 

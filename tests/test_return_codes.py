@@ -8,7 +8,16 @@ as the launch and come back with a HIP error where there is no device.  On a mac
 launch kernels on the fake operands, so they are made only where no device is visible.
 
 A handler can be planned without a device where ``begin_forward`` allocates nothing: one workgroup per head, i.e. a plan
-for 64 sequences of 32 heads with at most 255 selected pages."""
+for 64 sequences of 32 heads with at most 255 selected pages.
+
+An operator has ONE entry; the table calls it in each of its FORMS (``"<entry>, <form>"``: one sequence = the batch
+``{1, 0, 0, 0, NULL}``, contiguous rows = stride 0, whole rows = ``tile_max_offset`` 0), with the arguments that make the form
+held fixed (``"=name"``: never varied).  Two forms that come to the same call are made once.
+
+The one-sequence tiles form of ``quest_append_estimate_batched`` makes the checks of the batched tiles form (``tile_max_offset``
+is exactly the row capacity rounded up to 8, rows 16-byte aligned), which a single sequence was once spared: its cases
+``n = 4`` (offset 104 is not 8), ``off = 112`` with stride 136, and ``o`` at addresses 24 and 18 are EINVAL, where the table
+first recorded a launch.  Rows like these could never be read back: the attention launch has always refused them."""
 import ctypes
 
 EINVAL, EUNSUPPORTED, ESTATE, ETOOLARGE = -1, -2, -3, -4
@@ -35,9 +44,11 @@ def _b(n_seqs=2, kv_stride=104, meta_stride=8):
     return Batch(n_seqs, kv_stride, meta_stride, 0, None)
 
 
-# entry -> ordered (argument, well-formed value); "h" = the handler, filled in per case
+# "<entry>[, <form>]" -> ordered (argument, well-formed value); "h" = the handler, filled in per case; "=name" = an argument
+# the form fixes (no case replaces it)
 def _entries():
     kv, b = _kv(), _b()
+    one, whole, contiguous = ("=batch", _b(1, 0, 0)), ("=off", 0), ("=stride", 0)
     att = [("h", None), ("q", ONE), ("o", ONE), ("kv", kv), ("hq", 32)]
     app = [("h", None), ("k", ONE), ("v", ONE), ("metadata", kv), ("q", ONE), ("o", ONE), ("kv", kv), ("hq", 32)]
     est = [("k", ONE), ("v", ONE), ("kv", kv), ("q", ONE), ("o", ONE), ("hq", 32)]
@@ -45,47 +56,65 @@ def _entries():
     return {
         "quest_decode_forward": att + tail,
         "quest_decode_forward_shared": att + tail,
-        "quest_decode_forward_shared_dyn": att + [("state", ONE)] + tail,
+        "quest_decode_forward_shared_batched, one sequence": att + [("state", ONE), one] + tail,
         "quest_decode_forward_shared_batched": att + [("state", ONE), ("batch", b)] + tail,
-        "quest_decode_append_forward_shared_dyn": app + [("state", ONE)] + tail,
+        "quest_decode_append_forward_shared_batched, one sequence": app + [("state", ONE), one] + tail,
         "quest_decode_append_forward_shared_batched": app + [("state", ONE), ("batch", b)] + tail,
-        "quest_decode_forward_fused_topk": att + [("scores", ONE), ("n", MAX_N), ("val_out", None), ("idx_out", None)] + tail,
-        "quest_decode_forward_fused_topk_strided": att + [("scores", ONE), ("n", MAX_N), ("stride", 104), ("val_out", None),
-                                                          ("idx_out", None)] + tail,
-        "quest_decode_forward_fused_topk_dyn": att + [("scores", ONE), ("stride", 104), ("n", MAX_N), ("state", ONE)] + tail,
-        "quest_decode_forward_fused_topk_tiles_dyn": att + [("scores", ONE), ("stride", TSTRIDE), ("n", MAX_N), ("off", OFF),
-                                                            ("state", ONE)] + tail,
-        "quest_decode_forward_fused_topk_batched": att + [("scores", ONE), ("stride", 104), ("n", MAX_N), ("state", ONE),
+        "quest_decode_forward_fused_topk, contiguous rows": att + [("scores", ONE), ("n", MAX_N), contiguous, ("val_out", None),
+                                                                   ("idx_out", None)] + tail,
+        "quest_decode_forward_fused_topk": att + [("scores", ONE), ("n", MAX_N), ("stride", 104), ("val_out", None),
+                                                  ("idx_out", None)] + tail,
+        "quest_decode_forward_fused_topk_batched, one sequence": att + [("scores", ONE), ("stride", 104), ("n", MAX_N), whole,
+                                                                        ("state", ONE), one] + tail,
+        "quest_decode_forward_fused_topk_batched, one sequence, tiles": att + [("scores", ONE), ("stride", TSTRIDE), ("n", MAX_N),
+                                                                               ("off", OFF), ("state", ONE), one] + tail,
+        "quest_decode_forward_fused_topk_batched": att + [("scores", ONE), ("stride", 104), ("n", MAX_N), whole, ("state", ONE),
                                                           ("batch", b)] + tail,
-        "quest_decode_forward_fused_topk_tiles_batched": att + [("scores", ONE), ("stride", TSTRIDE), ("n", MAX_N),
-                                                                ("off", OFF), ("state", ONE), ("batch", b)] + tail,
+        "quest_decode_forward_fused_topk_batched, tiles": att + [("scores", ONE), ("stride", TSTRIDE), ("n", MAX_N),
+                                                                 ("off", OFF), ("state", ONE), ("batch", b)] + tail,
         "quest_decode_forward_batched": att + [("indices", ONE), ("idx_stride", 8), ("state", ONE), ("batch", b)] + tail,
         "quest_decode_layer_fused_batched": app + [("n", MAX_N), ("state", ONE), ("batch", b), ("scores_out", None),
                                                    ("stride", 0)] + tail,
         "quest_append_kv_cache_decode": [("k", ONE), ("v", ONE), ("kv", kv), ("metadata", kv), ("stream", None)],
-        "quest_append_kv_cache_decode_dyn": [("k", ONE), ("v", ONE), ("kv", kv), ("metadata", kv), ("state", ONE),
-                                             ("stream", None)],
+        "quest_append_kv_cache_decode_batched, one sequence": [("k", ONE), ("v", ONE), ("kv", kv), ("metadata", kv),
+                                                               ("state", ONE), one, ("stream", None)],
         "quest_append_kv_cache_decode_batched": [("k", ONE), ("v", ONE), ("kv", kv), ("metadata", kv), ("state", ONE),
                                                  ("batch", b), ("stream", None)],
         "quest_append_kv_cache_prefill": [("k", ONE), ("v", ONE), ("append_len", 20), ("n_pages", 4), ("kv", kv),
                                           ("metadata", kv), ("stream", None)],
-        "quest_step_state_advance": [("state", ONE), ("kv_table", ONE), ("meta_table", ONE), ("page_size", 16),
-                                     ("max_kv", 104), ("max_meta", 8), ("stream", None)],
+        # (this entry checks the strides for every n_seqs: one sequence passes its capacities)
+        "quest_step_state_advance_batched, one sequence": [("state", ONE), ("kv_table", ONE), ("meta_table", ONE),
+                                                           ("page_size", 16), ("max_kv", 104), ("max_meta", 8),
+                                                           ("=batch", _b(1, 104, 8)), ("stream", None)],
         "quest_step_state_advance_batched": [("state", ONE), ("kv_table", ONE), ("meta_table", ONE), ("page_size", 16),
                                              ("max_kv", 104), ("max_meta", 8), ("batch", b), ("stream", None)],
         "quest_estimate_attn_score": [("q", ONE), ("o", ONE), ("hq", 32), ("n", MAX_N), ("metadata", kv), ("stream", None)],
         "quest_estimate_attn_score_batched": [("q", ONE), ("o", ONE), ("hq", 32), ("stride", 104), ("n", MAX_N),
                                               ("metadata", kv), ("state", ONE), ("batch", b), ("stream", None)],
-        "quest_append_estimate": est + [("n", MAX_N), ("metadata", kv), ("stream", None)],
-        "quest_append_estimate_strided": est + [("n", MAX_N), ("stride", 104), ("metadata", kv), ("stream", None)],
-        "quest_append_estimate_dyn": est + [("stride", 104), ("n", MAX_N), ("metadata", kv), ("state", ONE), ("stream", None)],
-        "quest_append_estimate_tiles_dyn": est + [("stride", TSTRIDE), ("n", MAX_N), ("off", OFF), ("metadata", kv),
-                                                  ("state", ONE), ("stream", None)],
-        "quest_append_estimate_batched": est + [("stride", 104), ("n", MAX_N), ("metadata", kv), ("state", ONE), ("batch", b),
-                                                ("stream", None)],
-        "quest_append_estimate_tiles_batched": est + [("stride", TSTRIDE), ("n", MAX_N), ("off", OFF), ("metadata", kv),
-                                                      ("state", ONE), ("batch", b), ("stream", None)],
+        "quest_append_estimate, contiguous rows": est + [("n", MAX_N), contiguous, ("metadata", kv), ("stream", None)],
+        "quest_append_estimate": est + [("n", MAX_N), ("stride", 104), ("metadata", kv), ("stream", None)],
+        "quest_append_estimate_batched, one sequence": est + [("stride", 104), ("n", MAX_N), whole, ("metadata", kv),
+                                                              ("state", ONE), one, ("stream", None)],
+        "quest_append_estimate_batched, one sequence, tiles": est + [("stride", TSTRIDE), ("n", MAX_N), ("off", OFF),
+                                                                     ("metadata", kv), ("state", ONE), one, ("stream", None)],
+        "quest_append_estimate_batched": est + [("stride", 104), ("n", MAX_N), whole, ("metadata", kv), ("state", ONE),
+                                                ("batch", b), ("stream", None)],
+        "quest_append_estimate_batched, tiles": est + [("stride", TSTRIDE), ("n", MAX_N), ("off", OFF), ("metadata", kv),
+                                                       ("state", ONE), ("batch", b), ("stream", None)],
     }
+
+
+def _call(ent, name, rep):
+    """(C entry, its arguments in order) of a case; the handler still as the "h" placeholder."""
+    args = dict(ent[name])
+    args.update(rep)
+    return name.split(",")[0], args
+
+
+def _key(v):
+    if isinstance(v, ctypes.Structure):
+        return tuple(_key(getattr(v, f)) for f, _ in v._fields_)
+    return v.value if isinstance(v, ctypes.c_void_p) else v
 
 
 # handler states: None = NULL handler, "new" = created, never planned, a dict = planned with these values
@@ -190,11 +219,19 @@ def _cases():
     n = "quest_append_kv_cache_prefill"
     out += [(n, None, {"append_len": 0}), (n, None, {"n_pages": 0}), (n, None, {"append_len": 50}),
             (n, None, {"append_len": 49})]
-    for n in ("quest_step_state_advance", "quest_step_state_advance_batched"):
+    for n in ("quest_step_state_advance_batched, one sequence", "quest_step_state_advance_batched"):
         out += [(n, None, {a: 0}) for a in ("page_size", "max_kv", "max_meta")]
     n = "quest_step_state_advance_batched"
     out += [(n, None, {"max_kv": 105}), (n, None, {"max_meta": 9})]
-    return [(name, st, rep) for name, st, rep in out if all(k in dict(ent[name]) for k in rep)]
+    out = [(name, st, rep) for name, st, rep in out if all(k in dict(ent[name]) for k in rep)]
+    seen, once = set(), []
+    for name, st, rep in out:  # two forms that come to the same call of the same entry: made once
+        entry, args = _call(ent, name, rep)
+        k = (entry, "new" if st == "new" else st and tuple(sorted(st.items())), tuple(_key(v) for v in args.values()))
+        if k not in seen:
+            seen.add(k)
+            once.append((name, st, rep))
+    return once
 
 
 def _run(lib, cases):
@@ -221,11 +258,10 @@ def _run(lib, cases):
 
     try:
         for name, st, rep in cases:
-            args = dict(ent[name])
-            args.update(rep)
+            entry, args = _call(ent, name, rep)
             if "h" in args:
                 args["h"] = handler(st)
-            code = getattr(lib, name)(*args.values())
+            code = getattr(lib, entry)(*args.values())
             codes.append(LAUNCHED if code > 0 else CODES[code])
     finally:
         for h in handlers.values():
@@ -259,20 +295,19 @@ def test_entry_return_codes_match_the_recorded_table():
 # one letter per case of _cases(), in order
 EXPECTED = """
 ISILSSIIIIIISISISISIILIIIIIIISSLLLLLLIILLLLISILSSIIIIIISISISISIILIIIIIILSSULULLLLLLLLLISILSSIIIIIIIISISISISIILIIIILLLSSL
-LLLLLLLLLLLISILSSIIIIISLILIIIISISISISIILIIIILLLSSLLLLLLIILLLLISILIISSIIIIIIIIIISISISISIIIIIILIIIILLLSSISISISISIIIIILLIII
-ILLLSSULULLLLLLLLLISILIISSIIIIIIISLILIIIISISISISIIIIIILIIIILLLSSISISISISIIIIILLIIIILLLSSULULLLIILLLLISILSSIIIIIIIISISISI
-SIILIIIIIILSSIILLLTSLLLLLLLIIILLLLISILSSIIIIIIIISISISISIILIIIIIILSSIIIIILILILITISLILLLLLLLLILLLLLLLIIILLLLISILSSIIIIIIII
-IISISISISIILIIIILLLSSIIIIILILILITISIILLLLLLLLILLLLLLLIIILLLLISILSSIIIIIIIIIISISISISIILIIIILLLSSIIIIIIIIIIITSSIIIIIIIIIII
-IIIIIIIILLLIILLIILUIIULIILLIILIIIIIIILIUUULIILLIILLIILLIILISILSSIIIIIIISLILIIIISISISISIILIIIILLLSSIIIIIIIIIIIIIIIILLLLLL
-LLILLLLLLLIIILLLLISILSSIIIIIIISLILIIIISISISISIILIIIILLLSSIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIIILLLIIILIIIUIIILIIILIIIIIIIIIII
-IIIILIIILIIILIIILIIIISILSSIIIIIIISLLLIIIISISISISILLIIIILLLSSLLLLLLIILLLLISILIIIIIIIIIIISLIIIIIISISISISIIIIIILIUIILLLSSIS
-ISISISIIIIIILIUIILLLSSIILLIIIIIIIISSLLLLLLLLLLSULULLULLLLLLLIILILILLLLIILIUIIIILLILILLLLIILIUIIIILLIIILILILLLLIILIUIILLL
-LILILLLLIILIUIILLLLIIIILLLLLILILLLLIILIUIILLLLILILLLLIILIUIILLLLIILILILLLLIIIIUIIIILLILILLLLIIIIUIIIILLIIILIIIILIIILIILI
-ILLLLIILIUIILLL0LLLLLLIIIILLLILIILLLLIILIUIILLLIILLILIIIIIIIILLLLLLLLLIIIILIILILILLLLIILIUIIIILLILILLLLIILIUIIIILLLLLLLL
-IIIILIILILILLLLIILIUIIIILLILILLLLIILIUIIIILLLLLILILILILLILLLLLLLLLIIIIILIILILILLLLIILIUIILLLLILILLLLIILIUIILLLIILLILILIL
-ILIILLLLLLLLLIIIIILIILILILLLLIILIUIILLLLILILLLLIILIUIILLLIILIIIIIIIIIIIIIIIIIIIIIIILLLLIIIIIILLLILIILILILLLLIILIUIILLLLI
-LILLLLIILIUIILLLIILLILIIIIIIIILLLLLLLLLIIIIIILLLILIILILILLLLIILIUIILLLLILILLLLIILIUIILLLIIIIIIIIIIIIIIIIIIIIIIIIIIIIIISI
-LILILSULIIILIIIIIIII
+LLLLLLLLLLLISILSSIIIIISILIIIISISISISIILIIIILLLSSLLLLLLIILLLLISILIISSIIIIIIIIIISISISISIIIIIILIIIILLLSSISISISISILLIIIILLLS
+SULULLLLLLLLLISILIISSIIIIIIISILIIIISISISISIIIIIILIIIILLLSSISISISISILLIIIILLLSSULULLLIILLLLISILSSIIIIIIIISISISISIILIIIIII
+LSSIILLLTSLLLLLLLIIILLLLISILSSIIIIIIIISISISISIILIIIIIILSSIIIILILILITISILLLLLLLLILLLLLLLIIILLLLISILSSIIIIIIIIIISISISISIIL
+IIIILLLSSIIIIILILILITISIILLLLLLLLILLLLLLLIIILLLLISILSSIIIIIIIIIISISISISIILIIIILLLSSIIIIIIIIIIITSSIIIIIIIIIIILIIIISIILLLI
+ILLIILUIIULIILLIILIIIIIIILIUUULIILLIILLIILLIILISILSSIIIIIIISILIIIISISISISIILIIIILLLSSIIIIIIIIIIIIIIIILLLLLLLLILLLLLLLIII
+LLLLISILSSIIIIIIISILIIIISISISISIILIIIILLLSSIIIIIIIIIIIIIIIIIIIIIIIIILIIIISIILLLIIILIIIUIIILIIILIIIIIIIIIIIIIIILIIILIIILI
+IILIIIISILSSIIIIIIISLLLIIIISISISISILLIIIILLLSSLLLLLLIILLLLISILIIIIIIIIIIISLIIIIIISISISISIIIIIILIUIILLLSSISISISISIILIUIIL
+LLSSILLIIIIIIIISSLLLLLLLLLSULULLULLLLLLLIILILILLLLIILIUIIIILLILIIILIUIIIILLIIILILILLLLIILIUIILLLLILIIILIUIILLLLIIIILLLLI
+LILLLLIILIUIILLLLILIIILIUIILLLLIILILILLLLIIIIUIIIILLILIIIIIUIIIILLIIILIIIILIIILIILIILLLLIILIUIILLL0LLLLLLIIIILLLILIILLLL
+IILIUIILLLIILLILIIIIIIIILLLLLLLLLIIIILIILILILLLLIILIUIIIILLILIIILIUIIIILLLLLLLLIIIILIILILILLLLIILIUIIIILLILIIILIUIIIILLL
+LILILILILILLLLLLLLLIIIIILIILILILLLLIILIUIILLLLILIIILIUIILLLIILLILILILILIILLLLLLLLLIIIIILIILILILLLLIILIUIILLLLILIIILIUIIL
+LLIIIIIIIIIIIIIIIIIIIIIILIIIIIILIIIIIILLILIILILILLLLIILIUIILLLLILIIILIUIILLLIILLILIIIIIIIILLLLLLLLLIIIIIILLILIILILILLLLI
+ILIUIILLLLILIIILIUIILLLIIIIIIIIIIIIIIIIIIIIIILIIIIIIISILILILSULIIILIIIIIIII
 """
 
 

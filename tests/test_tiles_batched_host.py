@@ -1,5 +1,5 @@
-"""Host side of the batched tiles launches (quest_append_estimate_tiles_batched /
-quest_decode_forward_fused_topk_tiles_batched): the symbols exist and are declared, malformed arguments are refused
+"""Host side of the tiles form (tile_max_offset != 0) of quest_append_estimate_batched /
+quest_decode_forward_fused_topk_batched: the entries carry the offset, malformed arguments are refused
 before anything is launched (no GPU needed), and the row layout arithmetic a batched score scratch relies on."""
 import ctypes
 
@@ -9,24 +9,21 @@ import pytest
 def test_batched_tiles_symbols_are_exported_and_declared():
     from quest_amd._lib import SIGNATURES, Batch, lib
 
-    for name in ("quest_append_estimate_tiles_batched", "quest_decode_forward_fused_topk_tiles_batched"):
+    for name in ("quest_append_estimate_batched", "quest_decode_forward_fused_topk_batched"):
         assert name in SIGNATURES, name
         assert getattr(lib, name) is not None
-        # the argument order of the *_batched entries plus tile_max_offset: one more u32, a quest_batch_t by value
-        assert Batch in SIGNATURES[name][1]
-    est, est_b = SIGNATURES["quest_append_estimate_batched"][1], SIGNATURES["quest_append_estimate_tiles_batched"][1]
-    assert est_b == est[:8] + [ctypes.c_uint32] + est[8:]
-    att, att_b = (SIGNATURES["quest_decode_forward_fused_topk_batched"][1],
-                  SIGNATURES["quest_decode_forward_fused_topk_tiles_batched"][1])
-    assert att_b == att[:8] + [ctypes.c_uint32] + att[8:]
+        args = SIGNATURES[name][1]
+        assert Batch in args  # a quest_batch_t by value
+        # tile_max_offset: the u32 behind (stride, max_n), the third of three
+        assert args[6:9] == [ctypes.c_uint32] * 3 and args[9] is not ctypes.c_uint32
 
 
 def test_batched_tiles_entries_validate_arguments_without_gpu():
     from quest_amd._kernels import tile_max_offset, tiles_row_stride
     from quest_amd._lib import Batch, PagedKV, lib
 
-    est = lib.quest_append_estimate_tiles_batched
-    att = lib.quest_decode_forward_fused_topk_tiles_batched
+    est = lib.quest_append_estimate_batched
+    att = lib.quest_decode_forward_fused_topk_batched
     one = ctypes.c_void_p(16)  # non-null, 16-byte aligned; never dereferenced by the checks
     kv = PagedKV(data=16, indices=16, indptr=16, num_heads=32, page_size=16, head_dim=128, page_budget=0,
                  last_page_len=1, last_page_idx=0, layout=0)
@@ -35,7 +32,6 @@ def test_batched_tiles_entries_validate_arguments_without_gpu():
     b2 = Batch(2, max_n + 4, 8, 0, None)
     EINVAL, ESTATE = -1, -3
     # ---- estimate side
-    assert est(one, one, kv, one, one, 32, stride, max_n, 0, kv, one, b2, None) == EINVAL            # no offset
     assert est(one, one, kv, one, one, 32, stride, max_n, off + 8, kv, one, b2, None) == EINVAL      # not max_n rounded up to 8
     assert est(one, one, kv, one, one, 32, off + 8, max_n, off, kv, one, b2, None) == EINVAL         # stride without room
     assert est(one, one, kv, one, one, 32, off, max_n, off, kv, one, b2, None) == EINVAL
@@ -47,7 +43,6 @@ def test_batched_tiles_entries_validate_arguments_without_gpu():
     h = ctypes.c_void_p()
     assert lib.quest_decode_handler_create(ctypes.byref(h), 0) == 0
     try:
-        assert att(h, one, one, kv, 32, one, stride, max_n, 0, one, b2, None, None) == EINVAL       # no offset
         assert att(h, one, one, kv, 32, one, max_n - 4, max_n, off, one, b2, None, None) == EINVAL  # stride < max_n
         assert att(h, one, one, kv, 32, one, stride, max_n, off, one, Batch(0, 0, 0, 0, None), None, None) == EINVAL
         assert att(h, one, one, kv, 32, one, stride, max_n, off, one, Batch(2, max_n, 8, 0, None), None, None) == EINVAL  # table stride < max_n + 1

@@ -280,6 +280,9 @@ static int launch_gemv(const GemvArgs& p, uint32_t virtual_rows, hipStream_t s) 
     if (virtual_rows / (8 * 4) >= kWant) return launch_gemv_rw<MODE, 8, 4, 2>(p, virtual_rows, s);
     if constexpr (!kPairs) {
         if (virtual_rows / (8 * 2) >= kWant) return launch_gemv_rw<MODE, 8, 2, 4>(p, virtual_rows, s);
+        // the staged vector is padded to whole rounds: U = 8 rounds (4096 halves) end at 28672 under the 60 KiB stage, U = 4
+        // rounds (2048) reach the 30720 the other two shapes serve
+        if (p.in_dim > 7 * 8 * kWave * kVec) return launch_gemv_rw<MODE, 8, 1, 4>(p, virtual_rows, s);
         return launch_gemv_rw<MODE, 8, 1, 8>(p, virtual_rows, s);
     } else {
         return launch_gemv_rw<MODE, 8, 2, 4>(p, virtual_rows, s);

@@ -26,9 +26,10 @@ def test_gemv_residual_and_norm_gemv_vs_fp32(in_dim, out_dim):
     h2 = h.clone()
     _kernels.decode_gemv_residual(x, w, h2)
     torch.testing.assert_close(h2.float(), h.float() + w.float() @ x.float(), **tol)
-    out = torch.empty(out_dim, device=DEV, dtype=torch.float16)
+    out = torch.full((out_dim,), float("nan"), device=DEV, dtype=torch.float16)
     _kernels.decode_norm_gemv(x, None, 0.0, w, out)
     torch.testing.assert_close(out.float(), w.float() @ x.float(), **tol)
+    out.fill_(float("nan"))
     _kernels.decode_norm_gemv(x, gamma, 1e-5, w, out)
     torch.testing.assert_close(out.float(), w.float() @ _rms(x, gamma, 1e-5), **tol)
 
@@ -42,7 +43,7 @@ def test_mlp_gate_up_vs_fp32(hidden, inter):
     gamma = (1 + 0.1 * torch.randn(hidden, generator=g, device=DEV, dtype=torch.float16)).contiguous()
     wg = (torch.randn(inter, hidden, generator=g, device=DEV, dtype=torch.float16) * 0.05).contiguous()
     wu = (torch.randn(inter, hidden, generator=g, device=DEV, dtype=torch.float16) * 0.05).contiguous()
-    act = torch.empty(inter, device=DEV, dtype=torch.float16)
+    act = torch.full((inter,), float("nan"), device=DEV, dtype=torch.float16)
     _kernels.decode_mlp_gate_up(h, gamma, 1e-6, wg, wu, act)
     n = _rms(h, gamma, 1e-6)
     ref = torch.nn.functional.silu(wg.float() @ n) * (wu.float() @ n)
@@ -62,9 +63,9 @@ def test_qkv_rope_vs_fp32(Hq, Hkv, D, pos, scale, theta):
     wq = (torch.randn(Hq * D, hidden, generator=g, device=DEV, dtype=torch.float16) * s).contiguous()
     wk = (torch.randn(Hkv * D, hidden, generator=g, device=DEV, dtype=torch.float16) * s).contiguous()
     wv = (torch.randn(Hkv * D, hidden, generator=g, device=DEV, dtype=torch.float16) * s).contiguous()
-    q = torch.empty(1, Hq, D, device=DEV, dtype=torch.float16)
-    k = torch.empty(1, Hkv, D, device=DEV, dtype=torch.float16)
-    v = torch.empty(1, Hkv, D, device=DEV, dtype=torch.float16)
+    q = torch.full((1, Hq, D), float("nan"), device=DEV, dtype=torch.float16)
+    k = torch.full((1, Hkv, D), float("nan"), device=DEV, dtype=torch.float16)
+    v = torch.full((1, Hkv, D), float("nan"), device=DEV, dtype=torch.float16)
     state = torch.tensor([pos + 1, 1, 1, 0, 1, 1, 0, 0], dtype=torch.int32, device=DEV)  # seq_len = pos + 1
     _kernels.decode_qkv_rope(h, gamma, 1e-5, wq, wk, wv, q, k, v, D, scale, theta, state)
     n = _rms(h, gamma, 1e-5)
@@ -110,7 +111,7 @@ def test_batched_gemv_residual_and_norm_gemv_vs_fp32(n, in_dim, out_dim):
     _kernels.decode_norm_gemv_batched(x, gamma, 1e-5, w, out)
     torch.testing.assert_close(out.float(), _rms_rows(x, gamma, 1e-5) @ w.float().T, **tol)
     # token i of the batch == the batch-1 launch on token i, up to the accumulation order
-    one = torch.empty(out_dim, device=DEV, dtype=torch.float16)
+    one = torch.full((out_dim,), float("nan"), device=DEV, dtype=torch.float16)
     _kernels.decode_norm_gemv(x[n - 1], gamma, 1e-5, w, one)
     torch.testing.assert_close(out[n - 1].float(), one.float(), **tol)
 

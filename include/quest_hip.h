@@ -179,7 +179,8 @@ int quest_decode_end_forward(quest_decode_handler_t* h);
 /* forward: q, o: [1][num_qo_heads][head_dim]; paged_kv.indices = [num_qo_heads][page_budget]
  * selected physical pages (row stride paged_kv.page_budget), to which the sequence's last page
  * (last_page_idx, last_page_len tokens) is always added (decode_page.cuh:325-351).
- * lse: optional float[num_qo_heads] (natural log), may be NULL. */
+ * lse: optional float[num_qo_heads] (natural log), may be NULL; every entry below that takes `lse` writes the same quantity,
+ * the batched / state-driven ones as float[n_seqs][num_qo_heads] (row of sequence i at i * num_qo_heads). */
 int quest_decode_forward(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,
                          uint32_t num_qo_heads, float* lse, quest_stream_t stream);
 

@@ -105,3 +105,24 @@ def prefill_attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, causal:
         keep = torch.ones(qo_len, kv_len, dtype=torch.bool, device=q.device).tril(diagonal=kv_len - qo_len)
         logits = logits.masked_fill(~keep, float("-inf"))
     return torch.matmul(torch.softmax(logits, dim=-1), vh).transpose(0, 1)
+
+
+def lse_f64(q, keys):
+    """Log-sum-exp (natural log) of a decode token's attention scores, float64 numpy: ``q`` ``[Hq, D]``, ``keys``
+    ``[Hq, T, D]`` = the T tokens each query head attends (its selected pages' tokens plus the valid tokens of the current
+    page, as stored in the pool: fp16 values, or bf16 values held in any wider type).  Returns ``[Hq]`` float64:
+    ``log sum_t exp(q . k_t / sqrt(D))``."""
+    import numpy as np
+
+    q, keys = np.asarray(q, np.float64), np.asarray(keys, np.float64)
+    s = np.einsum("hd,htd->ht", q, keys) / math.sqrt(q.shape[-1])
+    m = s.max(axis=1, keepdims=True)
+    return (m + np.log(np.exp(s - m).sum(axis=1, keepdims=True)))[:, 0]
+
+
+def lse_f32(q, keys) -> torch.Tensor:
+    """The formula of ``lse_f64`` evaluated in float32 (``torch.logsumexp`` of float32 scores): the yardstick the LSE tests
+    size their bound with."""
+    q, keys = torch.as_tensor(q).float(), torch.as_tensor(keys).float()
+    s = torch.einsum("hd,htd->ht", q, keys) / math.sqrt(q.shape[-1])
+    return torch.logsumexp(s, dim=1)

@@ -724,6 +724,12 @@ def prefill_with_paged_kv_cache(q, kv_data, kv_indices, kv_last_page_len: int, c
 class BatchDecodeWithPagedKVCachePyTorchWrapper:
     """bsk_ops.h:88-117 / approx_attn.cu:27-150: begin_forward plans, forward launches."""
 
+    # EXTENSION: where every attention launch of this handler also writes the log-sum-exp (natural log) of its softmax
+    # denominators -- a float32 contiguous device tensor of at least ``n_seqs * num_qo_heads`` elements, row (sequence, head)
+    # at ``seq * num_qo_heads + head`` (the ``lse`` argument of include/quest_hip.h); None: no LSE is written.  What an
+    # integrator needs to merge the attention over two page sets.  The caller keeps the tensor alive while set.
+    lse_out = None
+
     def __init__(self, layout: int, *, dtype: torch.dtype = torch.float16):
         """``dtype`` (EXTENSION, keyword only): the element type this handler serves.  Constructed the reference's way it
         is fp16 and refuses everything else, like the reference's dispatch; ``dtype=torch.bfloat16`` makes a bf16 handler
@@ -758,6 +764,17 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         check(lib.quest_decode_begin_forward(self._h, n_sel, int(num_qo_heads), int(num_kv_heads), int(head_dim),
                                              int(page_size), stream), "BatchDecodeWithPagedKVCache")
 
+    def _lse(self, q):
+        """Pointer of ``lse_out`` for a launch over q ``[n_seqs, Hq, D]`` (None: the launch writes no LSE)."""
+        t = self.lse_out
+        if t is None:
+            return None
+        _check_input(t, "lse_out")
+        if t.dtype != torch.float32:
+            raise RuntimeError("lse_out must be a float32 tensor")
+        _check_ge(t.numel(), q.size(0) * q.size(1), "lse_out.numel(), n_seqs * num_qo_heads")
+        return t.data_ptr()
+
     def _check_dtype(self, q, *same) -> None:
         """q has the handler's element type and so have the call's other data tensors."""
         if q.dtype != self._dtype:
@@ -784,7 +801,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         self._check_dtype(q, o, paged_kv_data)
         kv = _paged(paged_kv_data, paged_kv_indices, paged_kv_indptr, paged_kv_last_page_len,
                     paged_kv_last_page_idx, self._layout, page_budget=paged_kv_indices.size(1))
-        check(lib.quest_decode_forward(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), None, _stream(q)),
+        check(lib.quest_decode_forward(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), self._lse(q), _stream(q)),
               "BatchDecodeWithPagedKVCache")
 
     def forward_shared(self, q, o, paged_kv_data, page_list, paged_kv_last_page_len: int,
@@ -800,7 +817,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_eq(page_list.dtype, torch.int32, "page_list.scalar_type(), torch::kInt32")
         self._check_dtype(q, o, paged_kv_data)
         kv = _paged(paged_kv_data, page_list, None, paged_kv_last_page_len, paged_kv_last_page_idx, self._layout)
-        return _launched(lib.quest_decode_forward_shared(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), None,
+        return _launched(lib.quest_decode_forward_shared(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), self._lse(q),
                                                          _stream(q)), "BatchDecodeWithPagedKVCache")
 
     def forward_fused_topk(self, q, o, paged_kv_data, page_table, scores, topk_val_out, topk_idx_out,
@@ -825,7 +842,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         return _launched(lib.quest_decode_forward_fused_topk(
             self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), scores.data_ptr(), scores.size(1), scores.stride(0),
             topk_val_out.data_ptr() if topk_val_out is not None else None,
-            topk_idx_out.data_ptr() if topk_idx_out is not None else None, None, _stream(q)), "BatchDecodeWithPagedKVCache")
+            topk_idx_out.data_ptr() if topk_idx_out is not None else None, self._lse(q), _stream(q)), "BatchDecodeWithPagedKVCache")
 
     # ---- state-driven launches (see the free functions above): n sequences per launch, one sequence = the batch of one in
     # its own shapes (state ``[8]``, tables ``[capacity]``, scores ``[Hq, stride]``)
@@ -843,7 +860,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         self._check_dtype(q, o, paged_kv_data)
         kv = _paged(paged_kv_data, kv_tables, None, 1, 0, self._layout)
         check(lib.quest_decode_forward_shared_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1),
-                                                      state.data_ptr(), b, None, _stream(q)),
+                                                      state.data_ptr(), b, self._lse(q), _stream(q)),
               "BatchDecodeWithPagedKVCache")
 
     def forward_shared_dyn(self, q, o, paged_kv_data, page_table, state) -> None:
@@ -867,7 +884,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         _check_eq(tuple(k.shape[-2:]), (kv.num_heads, kv.head_dim), "k.shape[-2:], (kv heads, head_dim)")
         meta = _paged(metadata_data, meta_tables, None, 1, 0, self._layout)
         return _launched(lib.quest_decode_append_forward_shared_batched(
-            self._h, k.data_ptr(), v.data_ptr(), meta, q.data_ptr(), o.data_ptr(), kv, q.size(1), state.data_ptr(), b, None,
+            self._h, k.data_ptr(), v.data_ptr(), meta, q.data_ptr(), o.data_ptr(), kv, q.size(1), state.data_ptr(), b, self._lse(q),
             _stream(q)), "BatchDecodeWithPagedKVCache")
 
     def append_forward_shared_dyn(self, k, v, metadata_data, meta_table, q, o, paged_kv_data, page_table, state) -> bool:
@@ -889,7 +906,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         self._check_dtype(q, o, paged_kv_data)
         kv = _paged(paged_kv_data, None, None, 1, 0, self._layout)
         check(lib.quest_decode_forward_batched(self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), indices.data_ptr(),
-                                               indices.size(2), state.data_ptr(), b, None, _stream(q)),
+                                               indices.size(2), state.data_ptr(), b, self._lse(q), _stream(q)),
               "BatchDecodeWithPagedKVCache")
 
     def forward_fused_topk_batched(self, q, o, paged_kv_data, kv_tables, scores, state, max_n_scores: int,
@@ -915,7 +932,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
             _check_ge(scores.size(2), tiles_row_stride(max_n_scores), "scores.size(2), tiles_row_stride(max_n_scores)")
         code = lib.quest_decode_forward_fused_topk_batched(
             self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), scores.data_ptr(), scores.size(2), int(max_n_scores),
-            tile_max_offset(max_n_scores) if tiles else 0, state.data_ptr(), b, None, _stream(q))
+            tile_max_offset(max_n_scores) if tiles else 0, state.data_ptr(), b, self._lse(q), _stream(q))
         if not tiles:  # whole rows are the caller's last route: QUEST_EUNSUPPORTED raises
             check(code, "BatchDecodeWithPagedKVCache")
         return _launched(code, "BatchDecodeWithPagedKVCache")
@@ -956,7 +973,7 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
             sc_ptr, sc_stride = scores_out.data_ptr(), scores_out.size(2)
         return _launched(lib.quest_decode_layer_fused_batched(
             self._h, k.data_ptr(), v.data_ptr(), meta, q.data_ptr(), o.data_ptr(), kv, q.size(1), int(max_n_scores),
-            state.data_ptr(), b, sc_ptr, sc_stride, None, _stream(q)), "BatchDecodeWithPagedKVCache")
+            state.data_ptr(), b, sc_ptr, sc_stride, self._lse(q), _stream(q)), "BatchDecodeWithPagedKVCache")
 
     # introspection used by the bench / tuning sweeps (not part of the reference surface)
     def plan_info(self):

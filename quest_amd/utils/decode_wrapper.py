@@ -37,6 +37,15 @@ class BatchDecodeWithPagedKVCacheWrapper:
                               paged_kv_last_page_idx, 1.0 if rope_scale is None else rope_scale,
                               1e4 if rope_theta is None else rope_theta)
 
+    @property
+    def lse_out(self):
+        """Where the handler's attention launches also write their log-sum-exp (``_kernels`` handler's ``lse_out``)."""
+        return self._wrapper.lse_out
+
+    @lse_out.setter
+    def lse_out(self, t) -> None:
+        self._wrapper.lse_out = t
+
     def __getattr__(self, name):
         """Everything beyond the reference's surface -- the fused, state-driven and batched launches, planning and
         inspection aids of ``_kernels.BatchDecodeWithPagedKVCachePyTorchWrapper`` -- is that object's own method."""

@@ -58,11 +58,70 @@ def oracle_pools(ctl, k, v):
     return kv, meta
 
 
-def used_pages_equal(dev_buf, ora, indices):
-    d = dev_buf.cpu().numpy().view(np.uint16)
-    o = ora.data.view(np.uint16)
-    idx = np.asarray(indices)
-    return np.array_equal(d[idx], o[idx])
+def _pools(ctl):
+    """(KV pool, metadata pool) of an ``InferenceController`` or a ``BatchedInferenceController``."""
+    if hasattr(ctl, "seqs"):
+        return ctl.kv_pool, ctl.metadata_pool
+    return ctl.kv_cache.pool, ctl.metadata_cache.pool
+
+
+def poison_pools(ctl, pattern: int) -> None:
+    """Fill the whole KV pool and the whole metadata pool (every layer, every page, reserved ones included) with one
+    16-bit pattern, before the first append: what ``torch.empty`` may hand out in service.  0x7fff is a NaN in fp16 and in
+    bf16; +inf is 0x7c00 (fp16) / 0x7f80 (bf16); 0 gives the zero-filled pool the poisoned run is compared with."""
+    p = int(pattern) & 0xFFFF
+    for pool in _pools(ctl):
+        pool.buf.view(torch.int16).fill_(p - 0x10000 if p & 0x8000 else p)
+
+
+def owned_mask(shape, layout, table, n_entries):
+    """Boolean mask over one pool layer ``shape`` (``[pages, 2, S, H, D]``, HND ``[pages, 2, H, S, D]``): entries
+    ``0 .. n_entries-1`` of the sequence whose page table is ``table``, K and V slot, every head slot (so NHD and NHD_ROT
+    give the same mask)."""
+    m = np.zeros(shape, bool)
+    S = shape[3] if layout == 1 else shape[2]
+    assert n_entries <= len(table) * S
+    for j, page in enumerate(table):
+        n = min(S, n_entries - j * S)
+        if n <= 0:
+            break
+        if layout == 1:
+            m[page, :, :, :n] = True
+        else:
+            m[page, :, :n] = True
+    return m
+
+
+def valid_mask(ctl, L):
+    """(KV mask, metadata mask) over the elements of one layer of both pools: what a sequence of ``L`` tokens owns -- the
+    first ``L`` token slots of its pages and one metadata entry per KV page.  For a ``BatchedInferenceController`` ``L`` is
+    one length per sequence and the masks are the union over the sequences of the shared pools."""
+    if hasattr(ctl, "seqs"):
+        masks = [valid_mask(c, l) for c, l in zip(ctl.seqs, L)]
+        return np.logical_or.reduce([m[0] for m in masks]), np.logical_or.reduce([m[1] for m in masks])
+    kvc, mc = ctl.kv_cache, ctl.metadata_cache
+    S = kvc.pool.block_len
+    n_pages = -(-L // S)
+    assert n_pages <= len(kvc.indicies) and -(-n_pages // S) <= len(mc.indicies)
+    return (owned_mask(tuple(kvc.pool.buf.shape[1:]), ctl.layout, kvc.indicies, L),
+            owned_mask(tuple(mc.pool.buf.shape[1:]), ctl.layout, mc.indicies, n_pages))
+
+
+def pool_bits(pool) -> np.ndarray:
+    """Every layer of a pool as uint16 bit patterns ``[layers, pages, 2, ...]``."""
+    return pool.buf.view(torch.int16).cpu().numpy().view(np.uint16)
+
+
+def unowned_bytes_untouched(ctl, L, pattern: int, layers=(0,)) -> bool:
+    """After launches on pools filled by ``poison_pools(ctl, pattern)``: every element outside ``valid_mask(ctl, L)`` of
+    the written ``layers``, and every element of the other layers, still holds the pattern."""
+    for pool, mask in zip(_pools(ctl), valid_mask(ctl, L)):
+        bits = pool_bits(pool)
+        for layer in range(bits.shape[0]):
+            stale = bits[layer] if layer not in layers else bits[layer][~mask]
+            if not (stale == np.uint16(pattern)).all():
+                return False
+    return True
 
 
 def gather_entries(buf: np.ndarray, indices, n_entries: int, layout: int):

@@ -84,7 +84,9 @@ def _check_half(x: torch.Tensor, op: str, *same) -> None:
 
 
 def _check_f16(x: torch.Tensor, op: str) -> None:
-    """The fp16-only operators (the decode-layer projections of csrc/decode_layer.hip)."""
+    """fp16 and nothing else: the check of an fp16-only operator.  (The decode-layer projections of csrc/decode_layer.hip
+    used it until they got their bf16 forms; no operator of this module is fp16-only any more, the one-launch layer
+    refuses bf16 in the library.)"""
     if x.dtype != torch.float16:
         raise RuntimeError(f"{op} failed to dispatch with dtype {x.dtype}")
 
@@ -340,71 +342,72 @@ def append_estimate(k, v, kv_data, kv_indices, kv_indptr, kv_last_page_len: int,
 
 # ---- decode-token projections of a decoder layer, fused (EXTENSION: csrc/decode_layer.hip)
 
-def _check_vec(x, n: int, name: str) -> None:
+# ``like``: the call's first data tensor -- fp16 or bf16, and every tensor of the call has its dtype (``_check_half``)
+def _check_vec(x, n: int, name: str, like) -> None:
     _check_input(x, name)
     _check_eq(x.numel(), n, f"{name}.numel(), {n}")
-    _check_f16(x, name)
+    _check_half(like, name, x)
 
 
-def _check_mat(x, n: int, cols: int, name: str) -> None:
+def _check_mat(x, n: int, cols: int, name: str, like) -> None:
     _check_input(x, name)
     _check_eq(x.numel(), n * cols, f"{name}.numel(), {n} * {cols}")
-    _check_f16(x, name)
+    _check_half(like, name, x)
 
 
-def _check_weight(w, out_dim: int, in_dim: int, name: str) -> None:
+def _check_weight(w, out_dim: int, in_dim: int, name: str, like) -> None:
     _check_input(w, name)
     _check_dim(2, w, name)
     _check_eq(tuple(w.shape), (out_dim, in_dim), f"{name}.shape, (out, in)")
-    _check_f16(w, name)
+    _check_half(like, name, w)
 
 
 def decode_norm_gemv(x, gamma, eps: float, w, out) -> None:
     """``out = w @ rmsnorm(x; gamma, eps)`` (``gamma`` None: ``out = w @ x``); x ``[in]``, w ``[out, in]``, out ``[out]``."""
     out_dim, in_dim = w.shape
-    _check_vec(x, in_dim, "x")
-    _check_vec(out, out_dim, "out")
-    _check_weight(w, out_dim, in_dim, "w")
+    _check_vec(x, in_dim, "x", x)
+    _check_vec(out, out_dim, "out", x)
+    _check_weight(w, out_dim, in_dim, "w", x)
     if gamma is not None:
-        _check_vec(gamma, in_dim, "gamma")
-    check(lib.quest_decode_norm_gemv(x.data_ptr(), gamma.data_ptr() if gamma is not None else None, float(eps),
-                                     w.data_ptr(), out.data_ptr(), in_dim, out_dim, _stream(x)), "decode_norm_gemv")
+        _check_vec(gamma, in_dim, "gamma", x)
+    check(lib.quest_decode_norm_gemv_dtype(x.data_ptr(), gamma.data_ptr() if gamma is not None else None, float(eps),
+                                     w.data_ptr(), out.data_ptr(), in_dim, out_dim, _DTYPES[x.dtype], _stream(x)), "decode_norm_gemv")
 
 
 def decode_gemv_residual(x, w, h) -> None:
     """``h += w @ x`` in place; x ``[in]``, w ``[out, in]``, h ``[out]``."""
     out_dim, in_dim = w.shape
-    _check_vec(x, in_dim, "x")
-    _check_vec(h, out_dim, "h")
-    _check_weight(w, out_dim, in_dim, "w")
-    check(lib.quest_decode_gemv_residual(x.data_ptr(), w.data_ptr(), h.data_ptr(), in_dim, out_dim, _stream(x)),
+    _check_vec(x, in_dim, "x", x)
+    _check_vec(h, out_dim, "h", x)
+    _check_weight(w, out_dim, in_dim, "w", x)
+    check(lib.quest_decode_gemv_residual_dtype(x.data_ptr(), w.data_ptr(), h.data_ptr(), in_dim, out_dim, _DTYPES[x.dtype], _stream(x)),
           "decode_gemv_residual")
 
 
 def decode_mlp_gate_up(h, gamma, eps: float, w_gate, w_up, act) -> None:
     """``act = silu(w_gate @ n) * (w_up @ n)`` with ``n = rmsnorm(h; gamma, eps)``."""
     inter, hidden = w_gate.shape
-    _check_vec(h, hidden, "h")
-    _check_vec(gamma, hidden, "gamma")
-    _check_vec(act, inter, "act")
-    _check_weight(w_gate, inter, hidden, "w_gate")
-    _check_weight(w_up, inter, hidden, "w_up")
-    check(lib.quest_decode_mlp_gate_up(h.data_ptr(), gamma.data_ptr(), float(eps), w_gate.data_ptr(), w_up.data_ptr(),
-                                       act.data_ptr(), hidden, inter, _stream(h)), "decode_mlp_gate_up")
+    _check_vec(h, hidden, "h", h)
+    _check_vec(gamma, hidden, "gamma", h)
+    _check_vec(act, inter, "act", h)
+    _check_weight(w_gate, inter, hidden, "w_gate", h)
+    _check_weight(w_up, inter, hidden, "w_up", h)
+    check(lib.quest_decode_mlp_gate_up_dtype(h.data_ptr(), gamma.data_ptr(), float(eps), w_gate.data_ptr(), w_up.data_ptr(),
+                                       act.data_ptr(), hidden, inter, _DTYPES[h.dtype], _stream(h)), "decode_mlp_gate_up")
 
 
 def _qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n: int):
     """Validation and leading C arguments shared by every q/k/v projection launch (``decode_qkv*``, ``decode_qkv_rope*``);
     ``n`` tokens."""
     hidden = wq.size(1)
-    _check_mat(h, n, hidden, "h")
-    _check_vec(gamma, hidden, "gamma")
-    _check_weight(wq, wq.size(0), hidden, "wq")
-    _check_weight(wk, wk.size(0), hidden, "wk")
-    _check_weight(wv, wk.size(0), hidden, "wv")
-    _check_mat(q, n, wq.size(0), "q")
-    _check_mat(k, n, wk.size(0), "k")
-    _check_mat(v, n, wk.size(0), "v")
+    _check_mat(h, n, hidden, "h", h)
+    _check_vec(gamma, hidden, "gamma", h)
+    _check_weight(wq, wq.size(0), hidden, "wq", h)
+    _check_weight(wk, wk.size(0), hidden, "wk", h)
+    _check_weight(wv, wk.size(0), hidden, "wv", h)
+    _check_mat(q, n, wq.size(0), "q", h)
+    _check_mat(k, n, wk.size(0), "k", h)
+    _check_mat(v, n, wk.size(0), "v", h)
     return (h.data_ptr(), gamma.data_ptr(), float(eps), wq.data_ptr(), wk.data_ptr(), wv.data_ptr(), q.data_ptr(),
             k.data_ptr(), v.data_ptr(), hidden)
 
@@ -424,7 +427,7 @@ def decode_qkv_rope(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, ro
     """q ``[1, Hq, D]``, k / v ``[1, Hkv, D]`` = projections of ``rmsnorm(h; gamma, eps)`` with RoPE on q and k at the
     position ``state.seq_len - 1`` (the device-resident step state, after ``step_state_advance_batched``)."""
     args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, state, 1)
-    check(lib.quest_decode_qkv_rope(*args, float(rope_scale), float(rope_theta), None, 1.0, state.data_ptr(), _stream(h)),
+    check(lib.quest_decode_qkv_rope_dtype(*args, float(rope_scale), float(rope_theta), None, 1.0, state.data_ptr(), _DTYPES[h.dtype], _stream(h)),
           "decode_qkv_rope")
 
 
@@ -433,14 +436,14 @@ def decode_qkv_rope_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: i
     """``decode_qkv_rope`` with the RoPE frequency table of ``apply_rope_in_place_freqs`` (llama3 / yarn)."""
     args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, state, 1)
     _check_rope_table(inv_freq, head_dim)
-    check(lib.quest_decode_qkv_rope(*args, 1.0, 1.0, inv_freq.data_ptr(), float(attention_factor), state.data_ptr(),
-                                    _stream(h)), "decode_qkv_rope_freqs")
+    check(lib.quest_decode_qkv_rope_dtype(*args, 1.0, 1.0, inv_freq.data_ptr(), float(attention_factor), state.data_ptr(),
+                                    _DTYPES[h.dtype], _stream(h)), "decode_qkv_rope_freqs")
 
 
 def decode_qkv(h, gamma, eps: float, wq, wk, wv, q, k, v) -> None:
     """q ``[1, Hq, D]``, k / v ``[1, Hkv, D]`` = projections of ``rmsnorm(h; gamma, eps)``, NOT rotated: the q-k-v launch of
     models with a per-head q/k norm, which ``apply_qk_norm_rope_in_place`` follows."""
-    check(lib.quest_decode_qkv(*_qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, 1), wq.size(0), wk.size(0), _stream(h)),
+    check(lib.quest_decode_qkv_dtype(*_qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, 1), wq.size(0), wk.size(0), _DTYPES[h.dtype], _stream(h)),
           "decode_qkv")
 
 
@@ -459,13 +462,13 @@ def decode_norm_gemv_batched(x, gamma, eps: float, w, out) -> None:
     out_dim, in_dim = w.shape
     n = x.numel() // in_dim
     _check_tokens(n)
-    _check_mat(x, n, in_dim, "x")
-    _check_mat(out, n, out_dim, "out")
-    _check_weight(w, out_dim, in_dim, "w")
+    _check_mat(x, n, in_dim, "x", x)
+    _check_mat(out, n, out_dim, "out", x)
+    _check_weight(w, out_dim, in_dim, "w", x)
     if gamma is not None:
-        _check_vec(gamma, in_dim, "gamma")
-    check(lib.quest_decode_norm_gemv_batched(x.data_ptr(), gamma.data_ptr() if gamma is not None else None, float(eps),
-                                             w.data_ptr(), out.data_ptr(), in_dim, out_dim, n, _stream(x)),
+        _check_vec(gamma, in_dim, "gamma", x)
+    check(lib.quest_decode_norm_gemv_batched_dtype(x.data_ptr(), gamma.data_ptr() if gamma is not None else None, float(eps),
+                                             w.data_ptr(), out.data_ptr(), in_dim, out_dim, n, _DTYPES[x.dtype], _stream(x)),
           "decode_norm_gemv_batched")
 
 
@@ -474,10 +477,10 @@ def decode_gemv_residual_batched(x, w, h) -> None:
     out_dim, in_dim = w.shape
     n = x.numel() // in_dim
     _check_tokens(n)
-    _check_mat(x, n, in_dim, "x")
-    _check_mat(h, n, out_dim, "h")
-    _check_weight(w, out_dim, in_dim, "w")
-    check(lib.quest_decode_gemv_residual_batched(x.data_ptr(), w.data_ptr(), h.data_ptr(), in_dim, out_dim, n, _stream(x)),
+    _check_mat(x, n, in_dim, "x", x)
+    _check_mat(h, n, out_dim, "h", x)
+    _check_weight(w, out_dim, in_dim, "w", x)
+    check(lib.quest_decode_gemv_residual_batched_dtype(x.data_ptr(), w.data_ptr(), h.data_ptr(), in_dim, out_dim, n, _DTYPES[x.dtype], _stream(x)),
           "decode_gemv_residual_batched")
 
 
@@ -486,13 +489,13 @@ def decode_mlp_gate_up_batched(h, gamma, eps: float, w_gate, w_up, act) -> None:
     inter, hidden = w_gate.shape
     n = h.numel() // hidden
     _check_tokens(n)
-    _check_mat(h, n, hidden, "h")
-    _check_vec(gamma, hidden, "gamma")
-    _check_mat(act, n, inter, "act")
-    _check_weight(w_gate, inter, hidden, "w_gate")
-    _check_weight(w_up, inter, hidden, "w_up")
-    check(lib.quest_decode_mlp_gate_up_batched(h.data_ptr(), gamma.data_ptr(), float(eps), w_gate.data_ptr(),
-                                               w_up.data_ptr(), act.data_ptr(), hidden, inter, n, _stream(h)),
+    _check_mat(h, n, hidden, "h", h)
+    _check_vec(gamma, hidden, "gamma", h)
+    _check_mat(act, n, inter, "act", h)
+    _check_weight(w_gate, inter, hidden, "w_gate", h)
+    _check_weight(w_up, inter, hidden, "w_up", h)
+    check(lib.quest_decode_mlp_gate_up_batched_dtype(h.data_ptr(), gamma.data_ptr(), float(eps), w_gate.data_ptr(),
+                                               w_up.data_ptr(), act.data_ptr(), hidden, inter, n, _DTYPES[h.dtype], _stream(h)),
           "decode_mlp_gate_up_batched")
 
 
@@ -503,8 +506,8 @@ def decode_qkv_rope_batched(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim:
     n = h.numel() // wq.size(1)
     _check_tokens(n)
     args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, states, n)
-    check(lib.quest_decode_qkv_rope_batched(*args, float(rope_scale), float(rope_theta), None, 1.0, states.data_ptr(), n,
-                                            _stream(h)), "decode_qkv_rope_batched")
+    check(lib.quest_decode_qkv_rope_batched_dtype(*args, float(rope_scale), float(rope_theta), None, 1.0, states.data_ptr(), n,
+                                            _DTYPES[h.dtype], _stream(h)), "decode_qkv_rope_batched")
 
 
 def decode_qkv_rope_batched_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, inv_freq,
@@ -514,16 +517,16 @@ def decode_qkv_rope_batched_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, hea
     _check_tokens(n)
     args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, states, n)
     _check_rope_table(inv_freq, head_dim)
-    check(lib.quest_decode_qkv_rope_batched(*args, 1.0, 1.0, inv_freq.data_ptr(), float(attention_factor),
-                                            states.data_ptr(), n, _stream(h)), "decode_qkv_rope_batched_freqs")
+    check(lib.quest_decode_qkv_rope_batched_dtype(*args, 1.0, 1.0, inv_freq.data_ptr(), float(attention_factor),
+                                            states.data_ptr(), n, _DTYPES[h.dtype], _stream(h)), "decode_qkv_rope_batched_freqs")
 
 
 def decode_qkv_batched(h, gamma, eps: float, wq, wk, wv, q, k, v) -> None:
     """``decode_qkv`` for n <= 16 tokens: h ``[n, hidden]``, q ``[n, Hq, D]``, k / v ``[n, Hkv, D]``."""
     n = h.numel() // wq.size(1)
     _check_tokens(n)
-    check(lib.quest_decode_qkv_batched(*_qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n), wq.size(0), wk.size(0), n,
-                                       _stream(h)), "decode_qkv_batched")
+    check(lib.quest_decode_qkv_batched_dtype(*_qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n), wq.size(0), wk.size(0), n,
+                                       _DTYPES[h.dtype], _stream(h)), "decode_qkv_batched")
 
 
 # ---- state-driven (graph-replayable) forms: EXTENSIONS, see include/quest_hip.h quest_step_state_t.  One launch serves

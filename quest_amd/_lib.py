@@ -106,6 +106,11 @@ SIGNATURES = {
     "quest_rms_norm_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_vp]),
     "quest_prefill_with_paged_kv_cache": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, PagedKV, c_u32, ctypes.c_int, c_vp]),
 }
+# the decode-layer projections' typed entries: <name>_dtype = <name> with `uint32_t dtype` in front of `stream`
+for _name in ("norm_gemv", "gemv_residual", "mlp_gate_up", "qkv_rope", "qkv"):
+    for _name in (f"quest_decode_{_name}", f"quest_decode_{_name}_batched"):
+        _res, _args = SIGNATURES[_name]
+        SIGNATURES[_name + "_dtype"] = (_res, _args[:-1] + [c_u32, _args[-1]])
 
 
 def verify_build(lib_path: str, src_root: str = None) -> None:

@@ -61,234 +61,19 @@ __device__ __forceinline__ void rope_cos_sin(const GemvArgs& p, uint32_t d, floa
 }
 
 typedef _Float16 half2_t __attribute__((ext_vector_type(2)));
+typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
 
+// 8 products of stored elements of type T onto an fp32 accumulator: four packed dots (v_dot2_f32_f16 / v_dot2c_f32_bf16)
+template <typename T>
 __device__ __forceinline__ float dot8(const half8& a, const half8& b, float acc) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
         const half2_t x = {a[2 * i], a[2 * i + 1]}, y = {b[2 * i], b[2 * i + 1]};
-        acc = __builtin_amdgcn_fdot2(x, y, acc, false);
+        if constexpr (kIsBf16<T>) acc = __builtin_amdgcn_fdot2_f32_bf16(__builtin_bit_cast(bf16x2, x), __builtin_bit_cast(bf16x2, y), acc, false);
+        else acc = __builtin_amdgcn_fdot2(x, y, acc, false);
     }
     return acc;
 }
-
-template <int MODE, int kGvWaves, int kGvRows, int kGvUnroll>
-__global__ __launch_bounds__(kGvWaves* kWave, kGvWaves / 2) void gemv_kernel(GemvArgs p) {  // 2 workgroups per CU
-    static_assert(MODE == kGvPlain || MODE == kGvResidual || kGvRows % 2 == 0, "pairs of row-dots stay in one wave");
-    extern __shared__ __attribute__((aligned(16))) unsigned char gv_smem[];
-    half_t* x_s = reinterpret_cast<half_t*>(gv_smem);  // in_dim halves, zero-padded to a multiple of 64 * 8 * kGvUnroll
-    __shared__ float s_part[kGvWaves];
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t n_vec = p.in_dim / kVec;
-    const uint32_t iters = (n_vec + kWave - 1) / kWave;
-    const uint32_t outer = (iters + kGvUnroll - 1) / kGvUnroll;
-
-    // ---- rows of this wave
-    const uint32_t vr0 = (blockIdx.x * kGvWaves + wave) * kGvRows;  // first virtual row-dot of the wave
-    const half_t* wrow[kGvRows];
-    uint32_t mat[kGvRows], row[kGvRows];
-    bool live[kGvRows];
-#pragma unroll
-    for (int r = 0; r < kGvRows; ++r) {
-        uint32_t vr = vr0 + r, m = 0, rr;
-        if constexpr (MODE == kGvSiluMul) {  // (gate, up) of the same output row side by side
-            m = vr & 1u;
-            rr = vr >> 1;
-            live[r] = rr < p.rows[0];
-        } else {
-            while (m < 2 && vr >= p.rows[m]) vr -= p.rows[m], ++m;
-            live[r] = vr < p.rows[m];
-            rr = vr;
-            if constexpr (MODE == kGvQkvRope) {
-                // pair-major order inside a head: virtual rows 2j, 2j+1 are features j and j + head_dim/2, so that a
-                // wave's 4 row-dots are two complete rotation pairs
-                const uint32_t hd = p.head_dim, head = rr / hd, j = rr % hd;
-                rr = head * hd + (j >> 1) + (j & 1u) * (hd / 2);
-            }
-        }
-        mat[r] = m;
-        row[r] = live[r] ? rr : 0u;
-        wrow[r] = p.w[live[r] ? m : 0] + (size_t)row[r] * p.in_dim;
-    }
-
-    // ---- the first weight loads leave before the input vector is staged (they do not depend on it).  Addressing: the
-    // row base is wave-uniform (an SGPR pair, advanced per round), the lane's part one 32-bit offset, the slot
-    // an immediate -- except in the last round of a row whose length is not a multiple of a round, where the vector index
-    // is clamped (kClamp).  A round = kGvUnroll slots x 64 lanes x 16 bytes per row.
-    constexpr uint32_t kRoundHalves = kGvUnroll * kWave * kVec;
-    const uint32_t full = n_vec / (kGvUnroll * kWave);  // rounds whose every slot lies inside the row for every lane
-    half8 wv[kGvUnroll][kGvRows];
-    const uint32_t lane_off = lane * kVec;
-    const half_t* const* rbase = wrow;  // (already wave-uniform for the compiler: built from blockIdx and the SGPR wave index)
-    // request round `o` of every row into slot u (kClamp: the round may reach past the row's end)
-    auto issue = [&](uint32_t o, int u, auto clamp_c) {
-        constexpr bool kClamp = decltype(clamp_c)::value;
-        if constexpr (!kClamp) {
-            const uint32_t off = lane_off + (uint32_t)u * (kWave * kVec);
-#pragma unroll
-            for (int r = 0; r < kGvRows; ++r) wv[u][r] = ld8_stream(rbase[r] + (size_t)o * kRoundHalves + off);
-        } else {
-            const uint32_t v = lane + (o * kGvUnroll + (uint32_t)u) * kWave, vc = v < n_vec ? v : n_vec - 1;
-#pragma unroll
-            for (int r = 0; r < kGvRows; ++r) wv[u][r] = ld8_stream(rbase[r] + (size_t)vc * kVec);
-        }
-    };
-    if (full > 0) {  // block-uniform
-#pragma unroll
-        for (int u = 0; u < kGvUnroll; ++u) issue(0, u, std::false_type{});
-    } else {
-#pragma unroll
-        for (int u = 0; u < kGvUnroll; ++u) issue(0, u, std::true_type{});
-    }
-
-    // ---- input vector -> LDS (RMSNorm prologue: x * rsqrt(mean(x^2) + eps) * gamma, rounded to fp16 like the
-    // stand-alone rms_norm_forward's output)
-    const uint32_t pad_vec = outer * kGvUnroll * kWave;  // vectors the loop touches
-    if (p.gamma) {
-        float ss = 0.f;
-        for (uint32_t v = tid; v < n_vec; v += kGvWaves * kWave) {
-            const float8 xf = to_f32<half_t>(ld8(p.x + (size_t)v * kVec));
-#pragma unroll
-            for (int i = 0; i < kVec; ++i) ss = __builtin_fmaf(xf[i], xf[i], ss);
-        }
-        ss = wave_allreduce_sum(ss, (int)lane);
-        if (lane == 0) s_part[wave] = ss;
-        __syncthreads();
-        float tot = 0.f;
-#pragma unroll
-        for (int w = 0; w < kGvWaves; ++w) tot += s_part[w];
-        const float inv = 1.0f / sqrtf(tot / (float)p.in_dim + p.eps);
-        for (uint32_t v = tid; v < pad_vec; v += kGvWaves * kWave) {
-            half8 o = (half8)(half_t)0;
-            if (v < n_vec) {
-                const float8 xf = to_f32<half_t>(ld8(p.x + (size_t)v * kVec)), g = to_f32<half_t>(ld8(p.gamma + (size_t)v * kVec));
-                float8 rr;
-#pragma unroll
-                for (int i = 0; i < kVec; ++i) rr[i] = xf[i] * inv * g[i];
-                o = __builtin_convertvector(rr, half8);
-            }
-            st8(x_s + (size_t)v * kVec, o);
-        }
-    } else {
-        for (uint32_t v = tid; v < pad_vec; v += kGvWaves * kWave)
-            st8(x_s + (size_t)v * kVec, v < n_vec ? ld8(p.x + (size_t)v * kVec) : (half8)(half_t)0);
-    }
-    __syncthreads();
-
-    // ---- stream the rows: a slot is re-issued for the next round as soon as it has been consumed (loads complete in
-    // order, so the wait for slot u leaves the younger ones in flight).  Three copies of the round body keep the
-    // steady state free of per-slot branches: next round full / next round clamped / last round.
-    float acc[kGvRows] = {};
-    auto consume = [&](uint32_t o, int u) {
-        const uint32_t v = lane + (o * kGvUnroll + (uint32_t)u) * kWave;
-        const half8 xv = ld8(x_s + (size_t)v * kVec);  // zero beyond in_dim: clamped weight vectors contribute nothing
-#pragma unroll
-        for (int r = 0; r < kGvRows; ++r) acc[r] = dot8(wv[u][r], xv, acc[r]);
-    };
-    for (uint32_t o = 0; o < outer; ++o) {
-        if (o + 1 < full) {
-#pragma unroll
-            for (int u = 0; u < kGvUnroll; ++u) {
-                consume(o, u);
-                issue(o + 1, u, std::false_type{});
-            }
-        } else if (o + 1 < outer) {
-#pragma unroll
-            for (int u = 0; u < kGvUnroll; ++u) {
-                consume(o, u);
-                issue(o + 1, u, std::true_type{});
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < kGvUnroll; ++u) consume(o, u);
-        }
-    }
-#pragma unroll
-    for (int r = 0; r < kGvRows; ++r) acc[r] = wave_allreduce_sum(acc[r], (int)lane);
-
-    // ---- epilogue (every lane holds the four totals; lane 0 writes)
-    if (lane != 0) return;
-    if constexpr (MODE == kGvPlain) {
-#pragma unroll
-        for (int r = 0; r < kGvRows; ++r)
-            if (live[r]) p.out[mat[r]][row[r]] = (half_t)acc[r];
-    } else if constexpr (MODE == kGvResidual) {
-#pragma unroll
-        for (int r = 0; r < kGvRows; ++r)
-            if (live[r]) p.out[0][row[r]] = (half_t)((float)p.residual[row[r]] + acc[r]);
-    } else if constexpr (MODE == kGvSiluMul) {
-#pragma unroll
-        for (int r = 0; r < kGvRows; r += 2)
-            if (live[r]) {
-                const float g = acc[r], u = acc[r + 1];
-                p.out[0][row[r]] = (half_t)(g / (1.0f + __expf(-g)) * u);
-            }
-    } else {  // kGvQkvRope
-        const float pos = (float)(p.state->seq_len - 1);
-#pragma unroll
-        for (int r = 0; r < kGvRows; r += 2) {
-            if (!live[r]) continue;
-            if (mat[r] < 2) {  // q / k: (acc[r], acc[r+1]) = features (d, d + D/2) of one head
-                float s, c;
-                rope_cos_sin(p, row[r] % p.head_dim, pos, c, s);  // row[r] % head_dim < D/2
-                p.out[mat[r]][row[r]] = (half_t)(acc[r] * c - acc[r + 1] * s);
-                p.out[mat[r]][row[r + 1]] = (half_t)(acc[r + 1] * c + acc[r] * s);
-            } else {
-                p.out[2][row[r]] = (half_t)acc[r];
-                p.out[2][row[r + 1]] = (half_t)acc[r + 1];
-            }
-        }
-    }
-}
-
-template <int MODE, int NWV, int RW, int U>
-static int launch_gemv_rw(const GemvArgs& p, uint32_t virtual_rows, hipStream_t s) {
-    const uint32_t n_vec = p.in_dim / kVec, iters = (n_vec + kWave - 1) / kWave;
-    const uint32_t outer = (iters + U - 1) / U;
-    const size_t lds = (size_t)outer * U * kWave * kVec * sizeof(half_t);
-    if (lds > 60 * 1024) return QUEST_EUNSUPPORTED;  // in_dim <= 30720
-    const uint32_t per_wg = NWV * RW;
-    hipLaunchKernelGGL((gemv_kernel<MODE, NWV, RW, U>), dim3((virtual_rows + per_wg - 1) / per_wg), dim3(NWV * kWave), lds, s, p);
-    QUEST_LAUNCH_CHECK();
-    return 0;
-}
-
-// 8-wave workgroups, 8 loads of 16 bytes in flight per lane (RW x U = 8: <= 100 VGPRs, two workgroups = 16 waves = 128 KiB
-// in flight per CU, the attention kernel's shape; 16 per lane needed 146-176 VGPRs and spilled under the 128 cap);
-// the largest rows-per-wave that still gives two workgroups per CU (512).  QUEST_GEMV_CFG="RW,U" forces one of the
-// built shapes (tuning).
-template <int MODE>
-static int launch_gemv(const GemvArgs& p, uint32_t virtual_rows, hipStream_t s) {
-    constexpr uint32_t kWant = 512;
-    static const int forced = [] {
-        const char* e = quest_tuning_env("QUEST_GEMV_CFG");
-        int rw = 0, u = 0;
-        return e && sscanf(e, "%d,%d", &rw, &u) == 2 ? rw * 100 + u : 0;
-    }();
-    constexpr bool kPairs = !(MODE == kGvPlain || MODE == kGvResidual);  // row-dots come in pairs: RW even
-    switch (forced) {
-        case 402: return launch_gemv_rw<MODE, 8, 4, 2>(p, virtual_rows, s);
-        case 204: return launch_gemv_rw<MODE, 8, 2, 4>(p, virtual_rows, s);
-        case 401: return launch_gemv_rw<MODE, 8, 4, 1>(p, virtual_rows, s);
-        case 202: return launch_gemv_rw<MODE, 8, 2, 2>(p, virtual_rows, s);
-        case 201: return launch_gemv_rw<MODE, 8, 2, 1>(p, virtual_rows, s);
-        case 104: if constexpr (!kPairs) return launch_gemv_rw<MODE, 8, 1, 4>(p, virtual_rows, s); break;
-        case 102: if constexpr (!kPairs) return launch_gemv_rw<MODE, 8, 1, 2>(p, virtual_rows, s); break;
-        case 108: if constexpr (!kPairs) return launch_gemv_rw<MODE, 8, 1, 8>(p, virtual_rows, s); break;
-        default: break;
-    }
-    if (virtual_rows / (8 * 4) >= kWant) return launch_gemv_rw<MODE, 8, 4, 2>(p, virtual_rows, s);
-    if constexpr (!kPairs) {
-        if (virtual_rows / (8 * 2) >= kWant) return launch_gemv_rw<MODE, 8, 2, 4>(p, virtual_rows, s);
-        // the staged vector is padded to whole rounds: U = 8 rounds (4096 halves) end at 28672 under the 60 KiB stage, U = 4
-        // rounds (2048) reach the 30720 the other two shapes serve
-        if (p.in_dim > 7 * 8 * kWave * kVec) return launch_gemv_rw<MODE, 8, 1, 4>(p, virtual_rows, s);
-        return launch_gemv_rw<MODE, 8, 1, 8>(p, virtual_rows, s);
-    } else {
-        return launch_gemv_rw<MODE, 8, 2, 4>(p, virtual_rows, s);
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------
 // The same four launches for n <= 16 decode tokens at once (one per sequence of a batch: BatchedInferenceController).
 // The weights are still read exactly once, so the launch is as HBM-bound as the batch-1 one, but 8 tokens x 2 flops per
@@ -338,194 +123,11 @@ __device__ __forceinline__ bool skinny_row(const GemvArgs& p, uint32_t vr, uint3
     return live;
 }
 
-template <int MODE, int NW, int U, int TG>
-__global__ __launch_bounds__(NW* kWave, 2) void skinny_kernel(SkinnyArgs a) {  // 8 waves per CU: <= 256 VGPRs
-    const GemvArgs& p = a.g;
-    extern __shared__ __attribute__((aligned(16))) unsigned char sk_smem[];
-    half_t* gamma_s = reinterpret_cast<half_t*>(sk_smem);  // RMSNorm weight (in_dim halves; launches with a prologue only)
-    __shared__ float s_ss[4 * TG][NW];                     // per token, per wave: sum of squares
-    __shared__ float s_part[NW][16][4 * TG];               // the waves' partial tiles [row][token]
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const uint32_t j = lane & 3u, blk = lane >> 2;  // B column (weight row of a quad) = A row (token of a group); k chunk
-
-    // ---- the lane's four weight rows (quad q: virtual row 16 block + 4 q + j) and TG input rows (token 4 t + j)
-    const half_t* wrow[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        uint32_t m, rr;
-        const bool live = skinny_row<MODE>(p, blockIdx.x * 16u + 4u * (uint32_t)q + j, m, rr);
-        wrow[q] = p.w[live ? m : 0] + (size_t)(live ? rr : 0u) * p.in_dim;  // dead rows read row 0 (never written out)
-    }
-    const half_t* xrow[TG];
-    bool tok[TG];
-#pragma unroll
-    for (int t = 0; t < TG; ++t) {
-        tok[t] = 4u * (uint32_t)t + j < a.n_tokens;
-        xrow[t] = p.x + (size_t)(tok[t] ? 4u * (uint32_t)t + j : 0u) * a.x_stride;
-    }
-    const bool norm = p.gamma != nullptr;  // block-uniform
-
-    const uint32_t n_steps = (p.in_dim + 127u) / 128u;
-    const uint32_t mine = wave < n_steps ? (n_steps - wave + NW - 1) / NW : 0u;  // this wave's steps
-    half8 wv[U][4], xv[U][TG];
-    auto issue = [&](uint32_t s, int u) {
-        const uint32_t k0 = (wave + NW * s) * 128u + blk * 8u;
-        const uint32_t kc = k0 < p.in_dim ? k0 : 0u;  // clamped; masked at use
-#pragma unroll
-        for (int q = 0; q < 4; ++q) wv[u][q] = ld8_stream(wrow[q] + kc);
-#pragma unroll
-        for (int t = 0; t < TG; ++t) xv[u][t] = ld8(xrow[t] + kc);
-    };
-#pragma unroll
-    for (int u = 0; u < U; ++u) issue((uint32_t)u, u);
-
-    // ---- RMSNorm prologue: 1 / rms of every token (every workgroup recomputes them; their loads queue behind the first
-    // weight fragments)
-    float inv[TG];
-#pragma unroll
-    for (int t = 0; t < TG; ++t) inv[t] = 1.0f;
-    if (norm) {
-        const uint32_t n_vec = p.in_dim / kVec;
-        for (uint32_t t = 0; t < a.n_tokens; ++t) {
-            float ss = 0.f;
-            for (uint32_t v = tid; v < n_vec; v += NW * kWave) {
-                const float8 xf = to_f32<half_t>(ld8(p.x + (size_t)t * a.x_stride + (size_t)v * kVec));
-#pragma unroll
-                for (int i = 0; i < kVec; ++i) ss = __builtin_fmaf(xf[i], xf[i], ss);
-            }
-            ss = wave_allreduce_sum(ss, (int)lane);
-            if (lane == 0) s_ss[t][wave] = ss;
-        }
-        for (uint32_t v = tid; v < n_vec; v += NW * kWave) st8(gamma_s + (size_t)v * kVec, ld8(p.gamma + (size_t)v * kVec));
-        __syncthreads();
-#pragma unroll
-        for (int t = 0; t < TG; ++t)
-            if (tok[t]) {
-                float tot = 0.f;
-#pragma unroll
-                for (int w = 0; w < NW; ++w) tot += s_ss[4 * t + j][w];
-                inv[t] = 1.0f / sqrtf(tot / (float)p.in_dim + p.eps);
-            }
-    }
-
-    // ---- stream
-    float4_t acc[4][TG];
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int t = 0; t < TG; ++t) acc[q][t] = float4_t{0.f, 0.f, 0.f, 0.f};
-    auto consume = [&](uint32_t s, int u) {
-        const uint32_t k0 = (wave + NW * s) * 128u + blk * 8u;
-        const bool in = k0 < p.in_dim;
-        float8 gf;
-        if (norm) gf = to_f32<half_t>(ld8(gamma_s + (in ? k0 : 0u)));
-#pragma unroll
-        for (int t = 0; t < TG; ++t) {
-            half8 b = xv[u][t];
-            if (norm) {
-                const float8 xf = to_f32<half_t>(b);
-                float8 rr;
-#pragma unroll
-                for (int i = 0; i < kVec; ++i) rr[i] = xf[i] * inv[t] * gf[i];
-                b = __builtin_convertvector(rr, half8);
-            }
-            if (!tok[t] || !in) b = (half8)(half_t)0;  // dead token / past the row's end: contributes nothing
-            const half4_t b0 = {b[0], b[1], b[2], b[3]}, b1 = {b[4], b[5], b[6], b[7]};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const half8 w8 = wv[u][q];
-                const half4_t w0 = {w8[0], w8[1], w8[2], w8[3]}, w1 = {w8[4], w8[5], w8[6], w8[7]};
-                acc[q][t] = __builtin_amdgcn_mfma_f32_4x4x4f16(b0, w0, acc[q][t], 0, 0, 0);  // A = tokens, B = weight rows
-                acc[q][t] = __builtin_amdgcn_mfma_f32_4x4x4f16(b1, w1, acc[q][t], 0, 0, 0);
-            }
-        }
-    };
-    const uint32_t rounds = (mine + U - 1) / U;
-    for (uint32_t o = 0; o < rounds; ++o) {
-        if (o + 1 < rounds) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                consume(o * U + (uint32_t)u, u);
-                issue((o + 1) * U + (uint32_t)u, u);
-            }
-        } else {
-#pragma unroll
-            for (int u = 0; u < U; ++u) consume(o * U + (uint32_t)u, u);
-        }
-    }
-    // ---- the 16 k chunks of the wave meet: lanes 4 b + j over b (distances 4, 8 inside a row of 16 lanes, then 16, 32);
-    // D element e of acc[q][t] at lane (b, j) = token 4 t + e, row 4 q + j
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-        for (int t = 0; t < TG; ++t)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                float v = acc[q][t][e];
-                v += dpp_f<kDppRowRor + 8>(v);
-                v += dpp_f<kDppRowRor + 4>(v);
-                v += lane_xor<16>(v, (int)lane);
-                v += lane_xor<32>(v, (int)lane);
-                if (lane < 4u) s_part[wave][4 * q + lane][4 * t + e] = v;
-            }
-    __syncthreads();
-
-    // ---- 128 threads: (token, row pair)
-    if (tid >= 128u) return;
-    const uint32_t token = tid & 15u, pair = tid >> 4;
-    if (token >= a.n_tokens) return;
-    float v0 = 0.f, v1 = 0.f;
-#pragma unroll
-    for (int w = 0; w < NW; ++w) v0 += s_part[w][2u * pair][token], v1 += s_part[w][2u * pair + 1u][token];
-    // the pair's two virtual rows -> (matrix, row)
-    uint32_t mat[2], row[2];
-    bool live[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) live[i] = skinny_row<MODE>(p, blockIdx.x * 16u + 2u * pair + (uint32_t)i, mat[i], row[i]);
-    if constexpr (MODE == kGvPlain) {
-        if (live[0]) p.out[mat[0]][(size_t)token * a.out_stride[mat[0]] + row[0]] = (half_t)v0;
-        if (live[1]) p.out[mat[1]][(size_t)token * a.out_stride[mat[1]] + row[1]] = (half_t)v1;
-    } else if constexpr (MODE == kGvResidual) {
-        const size_t base = (size_t)token * a.out_stride[0];
-        if (live[0]) p.out[0][base + row[0]] = (half_t)((float)p.residual[base + row[0]] + v0);
-        if (live[1]) p.out[0][base + row[1]] = (half_t)((float)p.residual[base + row[1]] + v1);
-    } else if constexpr (MODE == kGvSiluMul) {
-        if (live[0]) p.out[0][(size_t)token * a.out_stride[0] + row[0]] = (half_t)(v0 / (1.0f + __expf(-v0)) * v1);
-    } else {  // kGvQkvRope: rows come in (d, d + D/2) pairs of one head of one matrix
-        if (!live[0]) return;
-        half_t* o = p.out[mat[0]] + (size_t)token * a.out_stride[mat[0]];
-        if (mat[0] < 2) {
-            const float pos = (float)(p.state[(size_t)token * a.state_stride].seq_len - 1);
-            float sn, cs;
-            rope_cos_sin(p, row[0] % p.head_dim, pos, cs, sn);
-            o[row[0]] = (half_t)(v0 * cs - v1 * sn);
-            o[row[1]] = (half_t)(v1 * cs + v0 * sn);
-        } else {
-            o[row[0]] = (half_t)v0;
-            o[row[1]] = (half_t)v1;
-        }
-    }
-}
-
-// One 8-wave workgroup per CU (two waves per SIMD: 256 VGPRs each -- U x (4 + TG) fragments of 16 bytes in flight per lane
-// next to 16 TG accumulators; 128 KiB of weights in flight per CU at U = 4.  16 waves at 128 VGPRs spilled from TG = 2 on).
-// The fallback of the persistent kernel below: any n x in_dim, inputs from L2 (3.0-3.8 TB/s at 8 tokens).
-template <int MODE, int TG>
-static int launch_skinny_tg(const SkinnyArgs& a, uint32_t blocks, size_t lds, hipStream_t s) {
-    constexpr int U = TG <= 2 ? 4 : 2;
-    hipLaunchKernelGGL((skinny_kernel<MODE, 8, U, TG>), dim3(blocks), dim3(8 * kWave), lds, s, a);
-    QUEST_LAUNCH_CHECK();
-    return 0;
-}
-template <int MODE>
-static int launch_skinny(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_t s) {
-    const uint32_t blocks = (virtual_rows + 15u) / 16u;
-    const size_t lds = a.g.gamma ? (size_t)a.g.in_dim * sizeof(half_t) : 0;
-    if (lds > 48 * 1024) return QUEST_EUNSUPPORTED;  // in_dim <= 24576 with a RMSNorm prologue
-    if (a.n_tokens <= 4) return launch_skinny_tg<MODE, 1>(a, blocks, lds, s);
-    if (a.n_tokens <= 8) return launch_skinny_tg<MODE, 2>(a, blocks, lds, s);
-    return launch_skinny_tg<MODE, 4>(a, blocks, lds, s);
+// D += A B of sixteen 4 x 4 x 4 blocks of stored elements of type T (v_mfma_f32_4x4x4_16b_f16 / _bf16: one operand layout)
+template <typename T>
+__device__ __forceinline__ float4_t mfma_4x4x4(half4_t a, half4_t b, float4_t c) {
+    if constexpr (kIsBf16<T>) return __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(__builtin_bit_cast(bf16x4, a), __builtin_bit_cast(bf16x4, b), c, 0, 0, 0);
+    else return __builtin_amdgcn_mfma_f32_4x4x4f16(a, b, c, 0, 0, 0);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -570,249 +172,97 @@ struct PersistPlan {
 constexpr size_t kCuLdsBytes = 160 * 1024;
 constexpr size_t persist_lds_budget(uint32_t tg, bool rope) { return (size_t)(158 - tg * (2 + (rope ? 4 : 0))) * 1024; }
 
-template <int MODE, int TG, int CM>
-__global__ __launch_bounds__(kPsWaves* kWave, 4) void persist_kernel(SkinnyArgs a, PersistPlan pl) {
-    const GemvArgs& p = a.g;
-    constexpr int kXV = ps_input_vectors(TG);
-    extern __shared__ __attribute__((aligned(16))) unsigned char ps_smem[];
-    half_t* x_s = reinterpret_cast<half_t*>(ps_smem);  // [4 TG][x_row] (normalised) inputs
-    __shared__ float s_inv[4 * TG];
-    __shared__ float s_ssq[kXV][kPsWaves][2];  // RMSNorm prologue: per (input slot, wave) the sums of squares of its two tokens
-    __shared__ float s_part[2][kPsWaves][4][4 * TG];  // [buffer][wave = quad slot x slice][row of the quad][token]
-    // kGvQkvRope: (cos, sin) of every (token, frequency), computed once per workgroup while the first weights are on their
-    // way; a round's epilogue reads it (no sincosf, with its large-argument path, per round)
-    constexpr int kRopeMaxHalfD = 128;
-    __shared__ float2 s_rope[MODE == kGvQkvRope ? 4 * TG * kRopeMaxHalfD : 1];
-    static_assert(sizeof(s_inv) + sizeof(s_ssq) + sizeof(s_part) + sizeof(s_rope) + persist_lds_budget(TG, MODE == kGvQkvRope)
-                      <= kCuLdsBytes, "static arrays + the largest dynamic request must fit the CU's LDS");
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint32_t wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-#ifdef QUEST_PS_TIMELINE  // tuning build: s_memtime stamps of (workgroup 0 | last, wave 0 | 15) -> p.out[2] (16 x 4 x int64)
-    long long ps_t[16];
-    int ps_n = 0;
-#define PS_STAMP() do { if (ps_n < 16) ps_t[ps_n++] = (long long)__builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define PS_STAMP() do {} while (0)
-#endif
-    PS_STAMP();
-    const uint32_t j = lane & 3u, blk = lane >> 2;
-    const uint32_t ks = pl.ks, slice = wave & (ks - 1u), qslot = wave >> pl.ks_log2, qw = kPsWaves >> pl.ks_log2;
-    const bool norm = p.gamma != nullptr;
-    const uint32_t n_steps = (p.in_dim + 127u) / 128u;
-    // workgroup barrier that publishes LDS only: __syncthreads() also waits for the global loads in flight (vmcnt(0))
-    // whenever global stores are pending -- the epilogue's -- which would drain the prefetched set every round
-    auto lds_barrier = [] { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+}  // namespace quest
 
-    const uint32_t n_seg = pl.rounds;  // a segment = one round of tasks
-    auto seg_quad = [&](uint32_t seg) { return (seg * gridDim.x + blockIdx.x) * qw + qslot; };
-    auto row_ptr = [&](uint32_t quad) -> const half_t* {
-        uint32_t m, rr;
-        const bool live = quad < pl.n_quads && skinny_row<MODE>(p, 4u * quad + j, m, rr);
-        return p.w[live ? m : 0] + (size_t)(live ? rr : 0u) * p.in_dim;  // dead rows read row 0 (never written out)
-    };
-    // Every call requests exactly CM fragments, whatever the task: steps past the slice's end and quads past the matrix
-    // re-read cached bytes.  (A load under a branch makes the compiler's s_waitcnt bookkeeping assume it may not have been
-    // issued: every later wait for an OLDER load became vmcnt(0) -- the consumption of a set waited for the set requested
-    // just before it, i.e. nothing was in flight under the MFMAs.  For the same reason the requests past the last segment
-    // are issued all the same -- one cached line -- instead of being guarded.)
-    half8 wa[CM], wb[CM];
-    auto issue = [&](half8 (&w)[CM], uint32_t seg) {
-        const bool real = seg < n_seg;  // block-uniform; past the end: CM requests of ONE cached line, nobody waits for them
-        const half_t* wrow = real ? row_ptr(seg_quad(seg)) : p.w[0];
-        const uint32_t s1 = real ? n_steps : 0u;
-#pragma unroll
-        for (int i = 0; i < CM; ++i) {
-            const uint32_t st = slice + ks * (uint32_t)i, k0 = st * 128u + blk * 8u;
-            w[i] = ld8_stream(wrow + (st < s1 && k0 < p.in_dim ? k0 : 0u));
-        }
-    };
+// gemv_kernel, skinny_kernel, persist_kernel and their bf16 forms <name>_b16: decode_layer_kernels_typed.cuh, once per
+// element type.  (_b16, not the attention path's _bf16: tests/test_bf16_host.py counts the kernels named _bf16 against
+// the attention path's fp16 kernels, one twin each with the same template arguments, and these are not among them.)
+#define QUEST_ELEM half_t
+#define QUEST_KNAME(n) n
+#include "decode_layer_kernels_typed.cuh"
+#undef QUEST_ELEM
+#undef QUEST_KNAME
+#define QUEST_ELEM bf16_t
+#define QUEST_KNAME(n) n##_b16
+#include "decode_layer_kernels_typed.cuh"
+#undef QUEST_ELEM
+#undef QUEST_KNAME
 
-    // ---- the inputs: element e = tid + 1024 i -> (token e / vpp, vector e % vpp), vpp = 16 spp vectors per token (the
-    // host guarantees tokens x vpp <= kXV x 1024); always kXV loads (clamped)
-    const uint32_t vpp = pl.spp * 16u, x_tot = a.n_tokens * vpp;
-    half8 xr[kXV];
-    auto x_load = [&] {
-#pragma unroll
-        for (int i = 0; i < kXV; ++i) {
-            const uint32_t e = tid + (uint32_t)i * kPsWaves * kWave, t = __umulhi(e, pl.vpp_magic), k0 = (e - t * vpp) * kVec;
-            const bool in = e < x_tot && k0 < p.in_dim;
-            xr[i] = ld8(p.x + (in ? (size_t)t * a.x_stride + k0 : (size_t)0));
-        }
-    };
-    auto x_store = [&](half_t* dst) {  // zero for dead tokens and past the row's end
-#pragma unroll
-        for (int i = 0; i < kXV; ++i) {
-            const uint32_t e = tid + (uint32_t)i * kPsWaves * kWave, t = __umulhi(e, pl.vpp_magic), v = e - t * vpp;
-            if (e >= 4u * TG * vpp) continue;
-            half8 o = xr[i];
-            const bool in = e < x_tot && v * kVec < p.in_dim;
-            if (norm && in) {
-                const float8 xf = to_f32<half_t>(o), g = to_f32<half_t>(ld8(p.gamma + v * kVec));
-                const float inv = s_inv[t];
-                float8 rr;
-#pragma unroll
-                for (int c = 0; c < kVec; ++c) rr[c] = xf[c] * inv * g[c];
-                o = __builtin_convertvector(rr, half8);
-            }
-            st8(dst + (size_t)t * pl.x_row + (size_t)v * kVec, in ? o : (half8)(half_t)0);
-        }
-    };
+namespace quest {
 
-    // ---- prologue: inputs first (see above)
-    x_load();
-    if constexpr (MODE == kGvQkvRope) {  // under the inputs' latency; published by the staging barrier
-        const uint32_t half_d = p.head_dim / 2u;
-        for (uint32_t e = tid; e < a.n_tokens * half_d; e += kPsWaves * kWave) {
-            const uint32_t t = e / half_d, d = e % half_d;
-            const float pos = (float)(p.state[(size_t)t * a.state_stride].seq_len - 1);
-            float sn, cs;
-            rope_cos_sin(p, d, pos, cs, sn);
-            s_rope[t * kRopeMaxHalfD + d] = make_float2(cs, sn);
-        }
-    }
-
-    __builtin_amdgcn_s_barrier();
-    PS_STAMP();
-    if (norm) {
-        // 1 / rms per token.  A thread's vector i lies in ONE token and the lanes of a wave hold at most two tokens
-        // (vpp >= 64): every (slot i, wave) leaves the sums of its two sides t0, t0 + 1 in LDS, and wave t adds token t's
-        // entries in a FIXED order -- the result does not depend on the order in which the waves arrive (per-token LDS
-        // atomics did: two launches over the same inputs, or two workgroups of one launch, could normalise a token with
-        // 1 / rms values one fp32 ulp apart, and then differ in the fp16 rounding of an input).
-#pragma unroll
-        for (int i = 0; i < kXV; ++i) {
-            const uint32_t e = tid + (uint32_t)i * kPsWaves * kWave, t = __umulhi(e, pl.vpp_magic);
-            float ss = 0.f;
-            if (e < x_tot && (e - t * vpp) * kVec < p.in_dim) {
-                const float8 xf = to_f32<half_t>(xr[i]);
-#pragma unroll
-                for (int c = 0; c < kVec; ++c) ss = __builtin_fmaf(xf[c], xf[c], ss);
-            }
-            const uint32_t t0 = __builtin_amdgcn_readfirstlane(t);
-            const float s_lo = wave_allreduce_sum(t == t0 ? ss : 0.f, (int)lane), s_hi = wave_allreduce_sum(t == t0 ? 0.f : ss, (int)lane);
-            if (lane == 0) s_ssq[i][wave][0] = s_lo, s_ssq[i][wave][1] = s_hi;
-        }
-        __syncthreads();
-        if (wave < 4u * TG) {  // wave-uniform: wave t owns token t
-            float tot = 0.f;
-            for (uint32_t idx = lane; idx < (uint32_t)kXV * kPsWaves * 2u; idx += kWave) {
-                const uint32_t i = idx / (kPsWaves * 2u), w = (idx >> 1) % kPsWaves, side = idx & 1u;
-                const uint32_t tt = __umulhi(w * kWave + i * kPsWaves * kWave, pl.vpp_magic) + side;  // = that wave's t0 (+ 1)
-                tot += tt == wave ? s_ssq[i][w][side] : 0.f;
-            }
-            tot = wave_allreduce_sum(tot, (int)lane);
-            if (lane == 0) s_inv[wave] = 1.0f / sqrtf(tot / (float)p.in_dim + p.eps);
-        }
-        __syncthreads();
-    }
-    x_store(x_s);
-    PS_STAMP();
-    lds_barrier();
-    issue(wa, 0);
-    PS_STAMP();
-    float4_t acc[TG];
-#pragma unroll
-    for (int t = 0; t < TG; ++t) acc[t] = float4_t{0.f, 0.f, 0.f, 0.f};
-    auto consume = [&](const half8 (&w)[CM], uint32_t seg) {
-        if (seg_quad(seg) >= pl.n_quads) return;  // wave-uniform
-        const half_t* xb = x_s;
-#pragma unroll
-        for (int i = 0; i < CM; ++i) {
-            const uint32_t st = slice + ks * (uint32_t)i;
-            if (st < n_steps) {  // wave-uniform
-                const uint32_t kl = st * 128u + blk * 8u;
-                const half8 w8 = w[i];
-                const half4_t w0 = {w8[0], w8[1], w8[2], w8[3]}, w1 = {w8[4], w8[5], w8[6], w8[7]};
-#pragma unroll
-                for (int t = 0; t < TG; ++t) {
-                    const half8 x8 = ld8(xb + (size_t)(4u * (uint32_t)t + j) * pl.x_row + kl);
-                    const half4_t x0 = {x8[0], x8[1], x8[2], x8[3]}, x1 = {x8[4], x8[5], x8[6], x8[7]};
-                    acc[t] = __builtin_amdgcn_mfma_f32_4x4x4f16(x0, w0, acc[t], 0, 0, 0);  // A = tokens, B = weight rows
-                    acc[t] = __builtin_amdgcn_mfma_f32_4x4x4f16(x1, w1, acc[t], 0, 0, 0);
-                }
-            }
-        }
-    };
-    // the k slices of the quads meet; epilogue
-    auto finish = [&](uint32_t seg) {
-        const uint32_t buf = seg & 1u;
-#pragma unroll
-        for (int t = 0; t < TG; ++t)
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {  // D element e at lane (b, j) = token 4 t + e, row j of the quad; sum over b
-                float v = acc[t][e];
-                v += dpp_f<kDppRowRor + 8>(v);
-                v += dpp_f<kDppRowRor + 4>(v);
-                v += lane_xor<16>(v, (int)lane);
-                v += lane_xor<32>(v, (int)lane);
-                if (lane < 4u) s_part[buf][wave][lane][4 * t + e] = v;
-                acc[t][e] = 0.f;
-            }
-        lds_barrier();
-        // (quad slot, row pair, token) threads
-        const uint32_t token = tid & 15u, pair = (tid >> 4) & 1u, qs = tid >> 5;
-        if (qs >= qw || token >= a.n_tokens) return;
-        const uint32_t quad = (seg * gridDim.x + blockIdx.x) * qw + qs;
-        if (quad >= pl.n_quads) return;
-        float v0 = 0.f, v1 = 0.f;
-        for (uint32_t sl = 0; sl < ks; ++sl) {
-            v0 += s_part[buf][qs * ks + sl][2u * pair][token];
-            v1 += s_part[buf][qs * ks + sl][2u * pair + 1u][token];
-        }
-        uint32_t mat[2], row[2];
-        bool live[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) live[i] = skinny_row<MODE>(p, 4u * quad + 2u * pair + (uint32_t)i, mat[i], row[i]);
-        if constexpr (MODE == kGvPlain) {
-            if (live[0]) p.out[mat[0]][(size_t)token * a.out_stride[mat[0]] + row[0]] = (half_t)v0;
-            if (live[1]) p.out[mat[1]][(size_t)token * a.out_stride[mat[1]] + row[1]] = (half_t)v1;
-        } else if constexpr (MODE == kGvResidual) {
-            const size_t base = (size_t)token * a.out_stride[0];
-            if (live[0]) p.out[0][base + row[0]] = (half_t)((float)p.residual[base + row[0]] + v0);
-            if (live[1]) p.out[0][base + row[1]] = (half_t)((float)p.residual[base + row[1]] + v1);
-        } else if constexpr (MODE == kGvSiluMul) {
-            if (live[0]) p.out[0][(size_t)token * a.out_stride[0] + row[0]] = (half_t)(v0 / (1.0f + __expf(-v0)) * v1);
-        } else {  // kGvQkvRope: rows come in (d, d + D/2) pairs of one head of one matrix
-            if (!live[0]) return;
-            half_t* o = p.out[mat[0]] + (size_t)token * a.out_stride[mat[0]];
-            if (mat[0] < 2) {
-                const float2 r = s_rope[token * kRopeMaxHalfD + row[0] % p.head_dim];  // row[0] % head_dim < D / 2
-                const float cs = r.x, sn = r.y;
-                o[row[0]] = (half_t)(v0 * cs - v1 * sn);
-                o[row[1]] = (half_t)(v1 * cs + v0 * sn);
-            } else {
-                o[row[0]] = (half_t)v0;
-                o[row[1]] = (half_t)v1;
-            }
-        }
-    };
-    // Segment s: request segment s + 1, consume the set of s, let the slices meet.  A CU's memory
-    // pipeline holds ~64 KiB of requests; a wave whose requests do not fit stalls at issue.  Requested HERE, after the
-    // previous segment's barrier, a stalled wave holds nobody up; requested two segments ahead, right after the
-    // consumption and before the barrier, the stall sat in front of the barrier: 40.3 us instead of 36.8 for the gate/up
-    // launch (more in flight than the pipeline holds buys nothing).
-    auto body = [&](const half8 (&cur)[CM], half8 (&nxt)[CM], uint32_t sg) {
-        issue(nxt, sg + 1);
-        PS_STAMP();
-        consume(cur, sg);
-        PS_STAMP();
-        finish(sg);
-        PS_STAMP();
-    };
-    for (uint32_t seg = 0;; seg += 2) {  // wa holds segment seg; leaves by break (no merge with loads behind it)
-        body(wa, wb, seg);
-        if (seg + 1 >= n_seg) break;
-        body(wb, wa, seg + 1);
-        if (seg + 2 >= n_seg) break;
-    }
-    PS_STAMP();
-#ifdef QUEST_PS_TIMELINE
-    if (lane == 0 && (wave == 0 || wave == kPsWaves - 1) && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1) && p.out[2]) {
-        long long* o = reinterpret_cast<long long*>(p.out[2]) + ((blockIdx.x ? 2 : 0) + (wave ? 1 : 0)) * 16;
-        for (int i = 0; i < 16; ++i) o[i] = i < ps_n ? ps_t[i] : 0;
-    }
-#endif
+template <int MODE, int NWV, int RW, int U>
+static int launch_gemv_rw(const GemvArgs& p, uint32_t virtual_rows, hipStream_t s, bool bf) {
+    const uint32_t n_vec = p.in_dim / kVec, iters = (n_vec + kWave - 1) / kWave;
+    const uint32_t outer = (iters + U - 1) / U;
+    const size_t lds = (size_t)outer * U * kWave * kVec * sizeof(half_t);
+    if (lds > 60 * 1024) return QUEST_EUNSUPPORTED;  // in_dim <= 30720
+    const uint32_t per_wg = NWV * RW;
+    hipLaunchKernelGGL((bf ? gemv_kernel_b16<MODE, NWV, RW, U> : gemv_kernel<MODE, NWV, RW, U>), dim3((virtual_rows + per_wg - 1) / per_wg),
+                       dim3(NWV * kWave), lds, s, p);
+    QUEST_LAUNCH_CHECK();
+    return 0;
 }
+
+// 8-wave workgroups, 8 loads of 16 bytes in flight per lane (RW x U = 8: <= 100 VGPRs, two workgroups = 16 waves = 128 KiB
+// in flight per CU, the attention kernel's shape; 16 per lane needed 146-176 VGPRs and spilled under the 128 cap);
+// the largest rows-per-wave that still gives two workgroups per CU (512).  QUEST_GEMV_CFG="RW,U" forces one of the
+// built shapes (tuning).
+template <int MODE>
+static int launch_gemv(const GemvArgs& p, uint32_t virtual_rows, hipStream_t s, bool bf) {
+    constexpr uint32_t kWant = 512;
+    static const int forced = [] {
+        const char* e = quest_tuning_env("QUEST_GEMV_CFG");
+        int rw = 0, u = 0;
+        return e && sscanf(e, "%d,%d", &rw, &u) == 2 ? rw * 100 + u : 0;
+    }();
+    constexpr bool kPairs = !(MODE == kGvPlain || MODE == kGvResidual);  // row-dots come in pairs: RW even
+    switch (forced) {
+        case 402: return launch_gemv_rw<MODE, 8, 4, 2>(p, virtual_rows, s, bf);
+        case 204: return launch_gemv_rw<MODE, 8, 2, 4>(p, virtual_rows, s, bf);
+        case 401: return launch_gemv_rw<MODE, 8, 4, 1>(p, virtual_rows, s, bf);
+        case 202: return launch_gemv_rw<MODE, 8, 2, 2>(p, virtual_rows, s, bf);
+        case 201: return launch_gemv_rw<MODE, 8, 2, 1>(p, virtual_rows, s, bf);
+        case 104: if constexpr (!kPairs) return launch_gemv_rw<MODE, 8, 1, 4>(p, virtual_rows, s, bf); break;
+        case 102: if constexpr (!kPairs) return launch_gemv_rw<MODE, 8, 1, 2>(p, virtual_rows, s, bf); break;
+        case 108: if constexpr (!kPairs) return launch_gemv_rw<MODE, 8, 1, 8>(p, virtual_rows, s, bf); break;
+        default: break;
+    }
+    if (virtual_rows / (8 * 4) >= kWant) return launch_gemv_rw<MODE, 8, 4, 2>(p, virtual_rows, s, bf);
+    if constexpr (!kPairs) {
+        if (virtual_rows / (8 * 2) >= kWant) return launch_gemv_rw<MODE, 8, 2, 4>(p, virtual_rows, s, bf);
+        // the staged vector is padded to whole rounds: U = 8 rounds (4096 halves) end at 28672 under the 60 KiB stage, U = 4
+        // rounds (2048) reach the 30720 the other two shapes serve
+        if (p.in_dim > 7 * 8 * kWave * kVec) return launch_gemv_rw<MODE, 8, 1, 4>(p, virtual_rows, s, bf);
+        return launch_gemv_rw<MODE, 8, 1, 8>(p, virtual_rows, s, bf);
+    } else {
+        return launch_gemv_rw<MODE, 8, 2, 4>(p, virtual_rows, s, bf);
+    }
+}
+
+
+// One 8-wave workgroup per CU (two waves per SIMD: 256 VGPRs each -- U x (4 + TG) fragments of 16 bytes in flight per lane
+// next to 16 TG accumulators; 128 KiB of weights in flight per CU at U = 4.  16 waves at 128 VGPRs spilled from TG = 2 on).
+// The fallback of the persistent kernel below: any n x in_dim, inputs from L2 (3.0-3.8 TB/s at 8 tokens).
+template <int MODE, int TG>
+static int launch_skinny_tg(const SkinnyArgs& a, uint32_t blocks, size_t lds, hipStream_t s, bool bf) {
+    constexpr int U = TG <= 2 ? 4 : 2;
+    // bf16 at 9-16 tokens: one step in flight -- with two, the 16 accumulator tiles, the fragments and the bf16 conversions'
+    // temporaries do not fit the 256 registers (10-12 spilled; the fp16 kernel spills 8-10 there and is left as it is)
+    constexpr int UB = TG <= 2 ? 4 : 1;
+    hipLaunchKernelGGL((bf ? skinny_kernel_b16<MODE, 8, UB, TG> : skinny_kernel<MODE, 8, U, TG>), dim3(blocks), dim3(8 * kWave), lds, s, a);
+    QUEST_LAUNCH_CHECK();
+    return 0;
+}
+template <int MODE>
+static int launch_skinny(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_t s, bool bf) {
+    const uint32_t blocks = (virtual_rows + 15u) / 16u;
+    const size_t lds = a.g.gamma ? (size_t)a.g.in_dim * sizeof(half_t) : 0;
+    if (lds > 48 * 1024) return QUEST_EUNSUPPORTED;  // in_dim <= 24576 with a RMSNorm prologue
+    if (a.n_tokens <= 4) return launch_skinny_tg<MODE, 1>(a, blocks, lds, s, bf);
+    if (a.n_tokens <= 8) return launch_skinny_tg<MODE, 2>(a, blocks, lds, s, bf);
+    return launch_skinny_tg<MODE, 4>(a, blocks, lds, s, bf);
+}
+
 
 constexpr int kMaxDevices = 64;
 static int current_device() {  // index into the per-device caches below; -1: unknown (no caching)
@@ -822,19 +272,21 @@ static int current_device() {  // index into the per-device caches below; -1: un
 }
 
 template <int MODE, int TG>
-static int launch_persist_tg(const SkinnyArgs& a, const PersistPlan& pl, uint32_t grid, size_t lds, hipStream_t s) {
-    // more than 64 KiB of dynamic LDS needs the opt-in, once per DEVICE (a process may drive several GPUs) -- kept in a
+static int launch_persist_tg(const SkinnyArgs& a, const PersistPlan& pl, uint32_t grid, size_t lds, hipStream_t s, bool bf) {
+    // more than 64 KiB of dynamic LDS needs the opt-in, once per KERNEL and DEVICE (a process may drive several GPUs) -- kept in a
     // per-device table of atomics so that two threads launching on different devices do not race on one flag
-    static std::atomic<bool> attr[kMaxDevices];
+    static std::atomic<bool> attr[2][kMaxDevices];  // [element type][device]
     const int dev = current_device();
-    if (dev < 0 || !attr[dev].load(std::memory_order_acquire)) {
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&persist_kernel<MODE, TG, kCM>),
+    if (dev < 0 || !attr[bf][dev].load(std::memory_order_acquire)) {
+        const hipError_t e = hipFuncSetAttribute(bf ? reinterpret_cast<const void*>(&persist_kernel_b16<MODE, TG, kCM>)
+                                                    : reinterpret_cast<const void*>(&persist_kernel<MODE, TG, kCM>),
                                                  hipFuncAttributeMaxDynamicSharedMemorySize,
                                                  (int)persist_lds_budget(TG, MODE == kGvQkvRope));
         if (e != hipSuccess) return (int)e;
-        if (dev >= 0) attr[dev].store(true, std::memory_order_release);
+        if (dev >= 0) attr[bf][dev].store(true, std::memory_order_release);
     }
-    hipLaunchKernelGGL((persist_kernel<MODE, TG, kCM>), dim3(grid), dim3(kPsWaves * kWave), lds, s, a, pl);
+    hipLaunchKernelGGL((bf ? persist_kernel_b16<MODE, TG, kCM> : persist_kernel<MODE, TG, kCM>), dim3(grid), dim3(kPsWaves * kWave), lds, s,
+                       a, pl);
     QUEST_LAUNCH_CHECK();
     return 0;
 }
@@ -887,7 +339,7 @@ static uint32_t token_groups(uint32_t n_tokens) { return n_tokens <= 4 ? 1 : (n_
 // plan_as_rope: plan with the rotating q/k/v launch's (smaller) LDS budget, so that the unrotated q/k/v launch takes the
 // same n-token kernel as the rotating one at every shape (its v is then the same bits)
 template <int MODE>
-static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_t s, bool plan_as_rope = false) {
+static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_t s, bool bf, bool plan_as_rope = false) {
     if (a.n_tokens == 0 || a.n_tokens > 16) return QUEST_EINVAL;
     if (a.g.in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
     static const bool force_skinny = [] {
@@ -898,13 +350,13 @@ static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_
     PersistPlan pl{};
     uint32_t grid = 0;
     size_t lds = 0;
-    if (MODE == kGvQkvRope && a.g.head_dim > 256) return launch_skinny<MODE>(a, virtual_rows, s);  // (the LDS rotation table)
+    if (MODE == kGvQkvRope && a.g.head_dim > 256) return launch_skinny<MODE>(a, virtual_rows, s, bf);  // (the LDS rotation table)
     if (!force_skinny && plan_persist(a, virtual_rows, tg, MODE == kGvQkvRope || plan_as_rope, pl, grid, lds)) {
-        if (tg == 1) return launch_persist_tg<MODE, 1>(a, pl, grid, lds, s);
-        if (tg == 2) return launch_persist_tg<MODE, 2>(a, pl, grid, lds, s);
-        return launch_persist_tg<MODE, 4>(a, pl, grid, lds, s);
+        if (tg == 1) return launch_persist_tg<MODE, 1>(a, pl, grid, lds, s, bf);
+        if (tg == 2) return launch_persist_tg<MODE, 2>(a, pl, grid, lds, s, bf);
+        return launch_persist_tg<MODE, 4>(a, pl, grid, lds, s, bf);
     }
-    return launch_skinny<MODE>(a, virtual_rows, s);
+    return launch_skinny<MODE>(a, virtual_rows, s, bf);
 }
 
 }  // namespace quest
@@ -937,26 +389,29 @@ static SkinnyArgs skinny_args(const GemvArgs& g, uint32_t n_tokens) {
     return a;
 }
 
-extern "C" int quest_decode_norm_gemv(const void* x, const void* gamma, float eps, const void* w, void* out,
-                                      uint32_t in_dim, uint32_t out_dim, quest_stream_t stream) {
+extern "C" int quest_decode_norm_gemv_dtype(const void* x, const void* gamma, float eps, const void* w, void* out,
+                                      uint32_t in_dim, uint32_t out_dim, uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!x || !w || !out || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
     if (in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
-    return launch_gemv<kGvPlain>(plain_args(x, gamma, eps, w, out, in_dim, out_dim), out_dim, (hipStream_t)stream);
+    return launch_gemv<kGvPlain>(plain_args(x, gamma, eps, w, out, in_dim, out_dim), out_dim, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
 }
 
-extern "C" int quest_decode_gemv_residual(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
-                                          quest_stream_t stream) {
+extern "C" int quest_decode_gemv_residual_dtype(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
+                                          uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!x || !w || !h || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
     if (in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
-    return launch_gemv<kGvResidual>(residual_args(x, w, h, in_dim, out_dim), out_dim, (hipStream_t)stream);
+    return launch_gemv<kGvResidual>(residual_args(x, w, h, in_dim, out_dim), out_dim, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
 }
 
-extern "C" int quest_decode_mlp_gate_up(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
-                                        void* act, uint32_t hidden, uint32_t intermediate, quest_stream_t stream) {
+extern "C" int quest_decode_mlp_gate_up_dtype(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
+                                        void* act, uint32_t hidden, uint32_t intermediate, uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!h || !gamma || !w_gate || !w_up || !act || hidden == 0 || intermediate == 0) return QUEST_EINVAL;
     if (hidden % 8 != 0) return QUEST_EUNSUPPORTED;
     return launch_gemv<kGvSiluMul>(gate_up_args(h, gamma, eps, w_gate, w_up, act, hidden, intermediate), 2 * intermediate,
-                                   (hipStream_t)stream);
+                                   (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
 }
 
 // The rotating q-k-v launch: closed form (inv_freq NULL) or a frequency table, as quest_apply_rope_in_place_dtype.
@@ -964,7 +419,8 @@ extern "C" int quest_decode_mlp_gate_up(const void* h, const void* gamma, float 
 static int qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
                     void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
                     float rope_scale, float rope_theta, const float* inv_freq, float attention_factor,
-                    const quest_step_state_t* states, bool batched, uint32_t n_tokens, quest_stream_t stream) {
+                    const quest_step_state_t* states, bool batched, uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (inv_freq ? bad_rope_table(inv_freq, attention_factor) : (rope_scale == 0.f || rope_theta <= 0.f)) return QUEST_EINVAL;
     if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v || !states) return QUEST_EINVAL;
     if (hidden == 0 || num_qo_heads == 0 || num_kv_heads == 0) return QUEST_EINVAL;
@@ -979,20 +435,20 @@ static int qkv_rope(const void* h, const void* gamma, float eps, const void* wq,
     p.rcp_scale = inv_freq ? 1.0f : 1.0f / rope_scale, p.log2_rcp_theta = inv_freq ? 0.f : -log2f(rope_theta);
     p.inv_freq = inv_freq, p.attn_factor = inv_freq ? attention_factor : 1.0f;
     const uint32_t rows = p.rows[0] + p.rows[1] + p.rows[2];
-    if (!batched) return launch_gemv<kGvQkvRope>(p, rows, (hipStream_t)stream);
+    if (!batched) return launch_gemv<kGvQkvRope>(p, rows, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
     SkinnyArgs a = skinny_args(p, n_tokens);
     a.out_stride[1] = p.rows[1], a.out_stride[2] = p.rows[2];
     a.state_stride = 1;
-    return launch_batched<kGvQkvRope>(a, rows, (hipStream_t)stream);
+    return launch_batched<kGvQkvRope>(a, rows, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
 }
 
-extern "C" int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+extern "C" int quest_decode_qkv_rope_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                      const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
                                      uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
                                      const float* inv_freq, float attention_factor, const quest_step_state_t* state,
-                                     quest_stream_t stream) {
+                                     uint32_t dtype, quest_stream_t stream) {
     return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta,
-                    inv_freq, attention_factor, state, false, 0, stream);
+                    inv_freq, attention_factor, state, false, 0, dtype, stream);
 }
 
 // q, k, v projections WITHOUT the rotation (models with a per-head q/k norm between the projection and RoPE: the norm
@@ -1008,66 +464,131 @@ static GemvArgs qkv_args(const void* h, const void* gamma, float eps, const void
     return p;
 }
 
-extern "C" int quest_decode_qkv(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
+extern "C" int quest_decode_qkv_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void*
+                                      wv,
                                 void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows,
-                                quest_stream_t stream) {
+                                uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v) return QUEST_EINVAL;
     if (hidden == 0 || q_rows == 0 || kv_rows == 0) return QUEST_EINVAL;
     if (hidden % 8 != 0) return QUEST_EUNSUPPORTED;
     return launch_gemv<kGvPlain>(qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows), q_rows + 2 * kv_rows,
-                                 (hipStream_t)stream);
+                                 (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
 }
 
 // ---- the same for n_tokens <= 16 decode tokens (x: [n_tokens][in_dim], outputs [n_tokens][out_dim], contiguous)
-extern "C" int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out,
-                                              uint32_t in_dim, uint32_t out_dim, uint32_t n_tokens, quest_stream_t stream) {
+extern "C" int quest_decode_norm_gemv_batched_dtype(const void* x, const void* gamma, float eps, const void* w, void* out,
+                                              uint32_t in_dim, uint32_t out_dim, uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!x || !w || !out || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
     return launch_batched<kGvPlain>(skinny_args(plain_args(x, gamma, eps, w, out, in_dim, out_dim), n_tokens), out_dim,
-                                    (hipStream_t)stream);
+                                    (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
 }
 
-extern "C" int quest_decode_gemv_residual_batched(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
-                                                  uint32_t n_tokens, quest_stream_t stream) {
+extern "C" int quest_decode_gemv_residual_batched_dtype(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t
+                                                        out_dim,
+                                                  uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!x || !w || !h || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
     SkinnyArgs a = skinny_args(residual_args(x, w, h, in_dim, out_dim), n_tokens);
 #ifdef QUEST_PS_TIMELINE
     if (const char* e = quest_tuning_env("QUEST_PS_DEBUG_PTR")) a.g.out[2] = reinterpret_cast<half_t*>(strtoull(e, nullptr, 0));
 #endif
-    return launch_batched<kGvResidual>(a, out_dim, (hipStream_t)stream);
+    return launch_batched<kGvResidual>(a, out_dim, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
 }
 
-extern "C" int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma, float eps, const void* w_gate,
+extern "C" int quest_decode_mlp_gate_up_batched_dtype(const void* h, const void* gamma, float eps, const void* w_gate,
                                                 const void* w_up, void* act, uint32_t hidden, uint32_t intermediate,
-                                                uint32_t n_tokens, quest_stream_t stream) {
+                                                uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!h || !gamma || !w_gate || !w_up || !act || hidden == 0 || intermediate == 0) return QUEST_EINVAL;
     SkinnyArgs a = skinny_args(gate_up_args(h, gamma, eps, w_gate, w_up, act, hidden, intermediate), n_tokens);
-    return launch_batched<kGvSiluMul>(a, 2 * intermediate, (hipStream_t)stream);
+    return launch_batched<kGvSiluMul>(a, 2 * intermediate, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
 }
 
-extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+extern "C" int quest_decode_qkv_rope_batched_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                              const void* wv, void* q, void* k, void* v, uint32_t hidden,
                                              uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
                                              float rope_scale, float rope_theta, const float* inv_freq,
                                              float attention_factor, const quest_step_state_t* states, uint32_t n_tokens,
-                                             quest_stream_t stream) {
+                                             uint32_t dtype, quest_stream_t stream) {
     return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta,
-                    inv_freq, attention_factor, states, true, n_tokens, stream);
+                    inv_freq, attention_factor, states, true, n_tokens, dtype, stream);
 }
 
-extern "C" int quest_decode_qkv_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+extern "C" int quest_decode_qkv_batched_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                         const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows,
-                                        uint32_t kv_rows, uint32_t n_tokens, quest_stream_t stream) {
+                                        uint32_t kv_rows, uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v) return QUEST_EINVAL;
     if (hidden == 0 || q_rows == 0 || kv_rows == 0) return QUEST_EINVAL;
     SkinnyArgs a = skinny_args(qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows), n_tokens);
     a.out_stride[1] = a.out_stride[2] = kv_rows;
-    return launch_batched<kGvPlain>(a, q_rows + 2 * kv_rows, (hipStream_t)stream, true);
+    return launch_batched<kGvPlain>(a, q_rows + 2 * kv_rows, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16, true);
 }
 
-// Which kernel an n-token launch of this shape takes (tests / tuning; no launch): returns 1 and fills
+// ---- the untyped symbols: fp16
+extern "C" int quest_decode_norm_gemv(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
+                                      uint32_t out_dim, quest_stream_t stream) {
+    return quest_decode_norm_gemv_dtype(x, gamma, eps, w, out, in_dim, out_dim, QUEST_DTYPE_F16, stream);
+}
+extern "C" int quest_decode_gemv_residual(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
+                                          quest_stream_t stream) {
+    return quest_decode_gemv_residual_dtype(x, w, h, in_dim, out_dim, QUEST_DTYPE_F16, stream);
+}
+extern "C" int quest_decode_mlp_gate_up(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
+                                        void* act, uint32_t hidden, uint32_t intermediate, quest_stream_t stream) {
+    return quest_decode_mlp_gate_up_dtype(h, gamma, eps, w_gate, w_up, act, hidden, intermediate, QUEST_DTYPE_F16, stream);
+}
+extern "C" int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void*
+                                     wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t
+                                     num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta, const float*
+                                     inv_freq, float attention_factor, const quest_step_state_t* state, quest_stream_t stream)
+                                     {
+    return quest_decode_qkv_rope_dtype(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
+                                       rope_scale, rope_theta, inv_freq, attention_factor, state, QUEST_DTYPE_F16, stream);
+}
+extern "C" int quest_decode_qkv(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
+                                void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows, quest_stream_t
+                                stream) {
+    return quest_decode_qkv_dtype(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows, QUEST_DTYPE_F16, stream);
+}
+extern "C" int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t
+                                              in_dim, uint32_t out_dim, uint32_t n_tokens, quest_stream_t stream) {
+    return quest_decode_norm_gemv_batched_dtype(x, gamma, eps, w, out, in_dim, out_dim, n_tokens, QUEST_DTYPE_F16, stream);
+}
+extern "C" int quest_decode_gemv_residual_batched(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
+                                                  uint32_t n_tokens, quest_stream_t stream) {
+    return quest_decode_gemv_residual_batched_dtype(x, w, h, in_dim, out_dim, n_tokens, QUEST_DTYPE_F16, stream);
+}
+extern "C" int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma, float eps, const void* w_gate, const void*
+                                                w_up, void* act, uint32_t hidden, uint32_t intermediate, uint32_t n_tokens,
+                                                quest_stream_t stream) {
+    return quest_decode_mlp_gate_up_batched_dtype(h, gamma, eps, w_gate, w_up, act, hidden, intermediate, n_tokens,
+                                                  QUEST_DTYPE_F16, stream);
+}
+extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+                                             const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t
+                                             num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float
+                                             rope_theta, const float* inv_freq, float attention_factor, const
+                                             quest_step_state_t* states, uint32_t n_tokens, quest_stream_t stream) {
+    return quest_decode_qkv_rope_batched_dtype(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads,
+                                               head_dim, rope_scale, rope_theta, inv_freq, attention_factor, states, n_tokens,
+                                               QUEST_DTYPE_F16, stream);
+}
+extern "C" int quest_decode_qkv_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const
+                                        void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t
+                                        kv_rows, uint32_t n_tokens, quest_stream_t stream) {
+    return quest_decode_qkv_batched_dtype(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows, n_tokens,
+                                          QUEST_DTYPE_F16, stream);
+}
+
+// Which kernel an n-token launch of this shape takes, whatever its element type (both are 16 bits wide: the plan has no
+// dtype) (tests / tuning; no launch): returns 1 and fills
 // info = {k slices per quad, rounds, dynamic LDS bytes, workgroups, 128-wide k steps per row, fragments per set} for the
 // persistent kernel, 0 for the first (inputs-from-L2) kernel, < 0 for argument errors as the launches return them.
-extern "C" int quest_decode_batched_plan(uint32_t in_dim, uint32_t virtual_rows, uint32_t n_tokens, int rope, uint32_t info[6]) {
+extern "C" int quest_decode_batched_plan(uint32_t in_dim, uint32_t virtual_rows, uint32_t n_tokens, int rope, uint32_t
+                                         info[6]) {
     if (in_dim == 0 || virtual_rows == 0 || n_tokens == 0 || n_tokens > 16 || !info) return QUEST_EINVAL;
     if (in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
     SkinnyArgs a{};

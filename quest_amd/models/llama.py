@@ -149,7 +149,7 @@ class LlamaDecoderLayer(nn.Module):
         RMSNorm + gate/up + SiLU*up, down_proj + residual (csrc/decode_layer.hip; EXTENSION).  A model with a per-head q/k
         norm (Qwen3) takes FIVE: the norm needs a whole head row, which the q/k/v launch spreads over several workgroups,
         so that launch stores q, k, v unrotated and the q/k norm + RoPE launch follows.  ``h`` is the residual stream,
-        updated IN PLACE; fp16.  An ``InferenceController`` takes the batch-1 launches (``h`` ``[hidden]``), a
+        updated IN PLACE; fp16 or bf16.  An ``InferenceController`` takes the batch-1 launches (``h`` ``[hidden]``), a
         ``BatchedInferenceController`` the n-token ones at every n <= 16 (``h`` ``[n, hidden]``; the weights are read once
         per batch: persist_kernel) -- different kernels, whose results differ in the last bits."""
         a, m = self.self_attn, self.mlp
@@ -288,8 +288,9 @@ class LlamaForCausalLM(nn.Module):
         ``LlamaForCausalLM.from_pretrained(...)`` (scripts/bench_textgen.py:53-58, evaluation/*).  Parameter names
         are HF's (``model.layers.N.self_attn.q_proj.weight`` ...), so tensors are copied by name, shard by shard,
         straight to ``device``.  ``dtype``: float16 (default) or bfloat16 -- a bf16 checkpoint loads without a cast, and
-        with ``quest_init(dtype=torch.bfloat16)`` its KV cache, metadata and attention stay bf16 (the fused decode-layer
-        projections are fp16-only: a bf16 model's captured step takes the module path, ``fused_layers`` off)."""
+        with ``quest_init(dtype=torch.bfloat16)`` its KV cache, metadata and attention stay bf16.  The fused decode-layer
+        projections run both types, but a bf16 model's captured step takes them only on request
+        (``capture_decode_graph(fused_layers=True)``): by default it keeps the module path, see there."""
         import json
         import os
 
@@ -422,9 +423,14 @@ class LlamaForCausalLM(nn.Module):
     # ------------------------------------------------------------------ one hipGraph per generated token
     def capture_decode_graph(self, fused_layers: Optional[bool] = None) -> None:
         """Capture ONE decode step (all layers + lm_head) and keep it for ``decode_graph_step``.  ``fused_layers``
-        (default: on for fp16 models unless ``QUEST_FUSED_LAYER=0``): the decoder layers' projections, norms, RoPE,
+        (None, the default: on for fp16 models unless ``QUEST_FUSED_LAYER=0``, OFF for bf16 models; True / False: as
+        asked, for both types): the decoder layers' projections, norms, RoPE,
         activation and residual adds run as 4 fused HIP launches per layer (csrc/decode_layer.hip; 5 for a model with a
-        per-head q/k norm, ``forward_state_fused``) instead of ~14 rocBLAS / PyTorch launches.  Call after
+        per-head q/k norm, ``forward_state_fused``) instead of ~14 rocBLAS / PyTorch launches.  bf16 fused layers are
+        opt-in: the fused step rounds at other places than the module path (one rounding per launch instead of one per
+        module), so its logits differ from the module path's in the last bits, and callers of the default on bf16 models
+        rely on the module path; turning the default on for bf16 is a change of its own.  Inside the fused bf16 step the
+        attention is what a bf16 controller runs anyway (the two- / three-launch forms; no one-launch layer).  Call after
         the prompt has been processed (any length: while the cache holds fewer pages than the budget the
         sparse layers attend all of them, like the reference's full-attention branch).  The
         graph reads its input from ``self.graph_input`` ``[1, 1, hidden]`` and leaves the logits in
@@ -441,17 +447,18 @@ class LlamaForCausalLM(nn.Module):
         ctl.begin_graph_decode(dense_layers=m._quest_skip_layer > 0)
         self.graph_input = torch.zeros(n, 1, self.config.hidden_size, dtype=self.lm_head.weight.dtype, device=dev)
         self._graph_scores = qutils.score_scratch(ctl)
+        dtype = self.lm_head.weight.dtype
         if fused_layers is None:
             import os
 
-            fused_layers = os.environ.get("QUEST_FUSED_LAYER", "1") != "0"
-        fused_layers = (fused_layers and self.lm_head.weight.dtype == torch.float16 and n <= _kernels.MAX_BATCHED_TOKENS
-                        and fused_layer_launches_supported(self.config, n))
+            fused_layers = dtype == torch.float16 and os.environ.get("QUEST_FUSED_LAYER", "1") != "0"
+        fused_layers = (fused_layers and dtype in (torch.float16, torch.bfloat16) and ctl.dtype == dtype
+                        and n <= _kernels.MAX_BATCHED_TOKENS and fused_layer_launches_supported(self.config, n))
         self.fused_layers = fused_layers
         if fused_layers:
             # (kept on self: the captured launches hold these buffers' addresses)
-            ws = self._graph_ws = DecodeWorkspace(self.config, torch.float16, dev, n)
-            logits = torch.empty(n, 1, self.config.vocab_size, dtype=torch.float16, device=dev)
+            ws = self._graph_ws = DecodeWorkspace(self.config, dtype, dev, n)
+            logits = torch.empty(n, 1, self.config.vocab_size, dtype=dtype, device=dev)
             norm_gemv = _fused_layer_launches(ctl)[4]
 
             def step():
@@ -524,7 +531,8 @@ class LlamaForCausalLM(nn.Module):
     def capture_decode_graph_batched(self, fused_layers: Optional[bool] = None) -> None:
         """Batched ``capture_decode_graph``: input ``self.graph_input`` ``[n, 1, hidden]``, logits
         ``self.graph_logits`` ``[n, 1, vocab]``.  ``fused_layers`` as in ``capture_decode_graph`` (default on for fp16
-        models and n <= 16 unless ``QUEST_FUSED_LAYER=0``): 4 fused launches per layer for the whole batch."""
+        models and n <= 16 unless ``QUEST_FUSED_LAYER=0``, off for bf16 models, which take them with ``fused_layers=True``):
+        4 fused launches per layer for the whole batch."""
         self._capture_decode_graph(self.model.bController, fused_layers)
 
     def decode_graph_step_batched(self, input_ids: torch.Tensor) -> torch.Tensor:

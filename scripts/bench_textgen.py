@@ -13,6 +13,9 @@ lm_head -- is captured in a hipGraph and replayed.  First `skip` = 2 layers run 
     # Qwen3-8B shapes (per-head q/k norm, head_dim its own field); QUEST_FUSED_LAYER=0 takes the module path
     python scripts/bench_textgen.py --family qwen3 --layers 36 --heads 32 --kv-heads 8 --head-dim 128 --inter 12288 \
         --vocab 151936 --generate 64 [--seqs 8]
+    # a bf16 model (weights, KV cache, metadata): its captured step takes the fused decoder layers (fused_layers=True, which a
+    # bf16 model does not take by default); with QUEST_FUSED_LAYER=0 the same command times the module path
+    python scripts/bench_textgen.py --dtype bf16 --generate 64 [--seqs 8]
 """
 import argparse
 import json
@@ -21,6 +24,15 @@ import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
+
+
+DTYPES = {"f16": torch.float16, "bf16": torch.bfloat16}
+
+
+def fused_layers_arg(a):
+    """capture_decode_graph*'s fused_layers: the default for fp16 (on unless QUEST_FUSED_LAYER=0); bf16 fused layers are
+    opt-in, so asked for here -- unless QUEST_FUSED_LAYER=0 asks for the module path"""
+    return None if a.dtype == "f16" else os.environ.get("QUEST_FUSED_LAYER", "1") != "0"
 
 
 def time_decode(model, ctl, emb, reps):
@@ -53,19 +65,19 @@ def time_batched(cfg, a, dense, dev):
     import quest_amd.utils as qu
 
     with torch.device(dev):
-        model = LlamaForCausalLM(cfg).half()
+        model = LlamaForCausalLM(cfg).to(DTYPES[a.dtype])
     for p in model.parameters():
         p.data.normal_(0, 0.02)
     for m in model.modules():
         if hasattr(m, "variance_epsilon"):
             m.weight.data.fill_(1.0)
-    model.quest_init_batched(a.seqs, 16, a.ctx + 256, a.token_budget, kv_layout=a.layout)
+    model.quest_init_batched(a.seqs, 16, a.ctx + 256, a.token_budget, dtype=DTYPES[a.dtype], kv_layout=a.layout)
     if dense:
         model.model._quest_skip_layer = a.layers
     b = model.model.bController
     g = torch.Generator(device=dev).manual_seed(1)
     D = a.head_dim
-    k = torch.empty(a.ctx, a.kv_heads, D, dtype=torch.float16, device=dev)
+    k = torch.empty(a.ctx, a.kv_heads, D, dtype=DTYPES[a.dtype], device=dev)
     v = torch.empty_like(k)
     for c in b.seqs:
         c.prepare_metadata(a.ctx)
@@ -76,9 +88,9 @@ def time_batched(cfg, a, dense, dev):
             qu.append_kv(k, v, c, l)
         c.end_forward()
     del k, v
-    model.capture_decode_graph_batched()
+    model.capture_decode_graph_batched(fused_layers=fused_layers_arg(a))
     time_batched.fused_layers = bool(model.fused_layers)
-    model.graph_input.copy_(torch.randn(a.seqs, 1, a.hidden, generator=g, device=dev, dtype=torch.float16) * 0.1)
+    model.graph_input.copy_(torch.randn(a.seqs, 1, a.hidden, generator=g, device=dev, dtype=DTYPES[a.dtype]) * 0.1)
     for _ in range(3):
         model._graph.replay()
         b.prepare_metadata(1)
@@ -131,6 +143,8 @@ def main():
                     help="model family of the random-weight model: mistral = Llama arithmetic, qwen3 = per-head q/k RMSNorm "
                          "before RoPE; both run their default RoPE through the frequency table (theta 1e6)")
     ap.add_argument("--head-dim", type=int, default=None, help="head dimension (default: hidden / heads)")
+    ap.add_argument("--dtype", choices=["f16", "bf16"], default="f16",
+                    help="element type of the weights, the KV cache and the metadata; bf16 captures with fused_layers=True")
     a = ap.parse_args()
     from quest_amd.models.llama import LlamaConfig, LlamaForCausalLM
     import quest_amd.utils as qu
@@ -151,7 +165,7 @@ def main():
         import time
         t0 = time.perf_counter()
         with torch.device(dev):
-            tmp = LlamaForCausalLM(cfg).half()
+            tmp = LlamaForCausalLM(cfg).to(DTYPES[a.dtype])
         for p in tmp.parameters():
             p.data.normal_(0, 0.02)
         for m in tmp.modules():
@@ -177,7 +191,7 @@ def main():
         print(json.dumps({"bench": "e2e batched decode, random-weight Llama", "sequences": a.seqs, "ctx": a.ctx, "kv_layout": a.layout,
                           "token_budget": a.token_budget, "layers": a.layers, "hidden": a.hidden, "heads": a.heads,
                           "kv_heads": a.kv_heads, "intermediate": a.inter, "vocab": a.vocab, "dense_first_layers": 2,
-                          "family": a.family, "head_dim": a.head_dim,
+                          "family": a.family, "head_dim": a.head_dim, "dtype": a.dtype,
                           "fused_decoder_layer_launches": getattr(time_batched, "fused_layers", None), "ms_per_step_quest": q_ms,
                           "ms_per_step_full_kv": d_ms, "tokens_per_s_quest": a.seqs / (q_ms * 1e-3),
                           "tokens_per_s_full_kv": a.seqs / (d_ms * 1e-3), "speedup": d_ms / q_ms}))
@@ -189,23 +203,23 @@ def main():
         if a.checkpoint:
             import time
             t0 = time.perf_counter()
-            model = LlamaForCausalLM.from_pretrained(a.checkpoint, device=dev)
+            model = LlamaForCausalLM.from_pretrained(a.checkpoint, device=dev, dtype=DTYPES[a.dtype])
             ckpt_info["load_s"] = time.perf_counter() - t0
         else:
             with torch.device(dev):
-                model = LlamaForCausalLM(cfg).half()
+                model = LlamaForCausalLM(cfg).to(DTYPES[a.dtype])
             for p in model.parameters():
                 p.data.normal_(0, 0.02)
             for m in model.modules():
                 if hasattr(m, "variance_epsilon"):
                     m.weight.data.fill_(1.0)
-        model.quest_init(16, a.ctx + 256 + a.generate, budget, kv_layout=a.layout)
+        model.quest_init(16, a.ctx + 256 + a.generate, budget, dtype=DTYPES[a.dtype], kv_layout=a.layout)
         ctl = model.model.iController
         g = torch.Generator(device=dev).manual_seed(1)
         D = a.head_dim
         if a.real_prefill:
             import time
-            x = torch.randn(1, a.ctx, a.hidden, generator=g, device=dev, dtype=torch.float16)
+            x = torch.randn(1, a.ctx, a.hidden, generator=g, device=dev, dtype=DTYPES[a.dtype])
             with torch.inference_mode():
                 model(inputs_embeds=x[:, :256])  # warm the libraries' kernels on a short request, then start over
                 model.quest_clear()
@@ -219,7 +233,7 @@ def main():
         else:
             ctl.prepare_metadata(a.ctx)
             ctl.begin_forward(a.ctx)
-            k = torch.empty(a.ctx, a.kv_heads, D, dtype=torch.float16, device=dev)
+            k = torch.empty(a.ctx, a.kv_heads, D, dtype=DTYPES[a.dtype], device=dev)
             v = torch.empty_like(k)
             for l in range(a.layers):
                 k.normal_(generator=g)
@@ -227,12 +241,12 @@ def main():
                 qu.append_kv(k, v, ctl, l)
             ctl.end_forward()
             del k, v
-        emb = torch.randn(1, 1, a.hidden, generator=g, device=dev, dtype=torch.float16) * 0.1
+        emb = torch.randn(1, 1, a.hidden, generator=g, device=dev, dtype=DTYPES[a.dtype]) * 0.1
         results[name] = time_decode(model, ctl, emb, a.reps)
         if a.generate:
             # greedy generation by one graph replay per token (device-resident lengths; the host only feeds the token)
             import time
-            model.capture_decode_graph()
+            model.capture_decode_graph(fused_layers=fused_layers_arg(a))
             gen_fused = bool(model.fused_layers)
             tok = torch.zeros(1, 1, dtype=torch.long, device=dev)
             with torch.inference_mode():
@@ -249,7 +263,7 @@ def main():
     out = {"bench": "e2e decode latency, random-weight Llama", "ctx": a.ctx, "token_budget": a.token_budget,
            "page_budget_pages": a.token_budget // 16, "layers": a.layers, "hidden": a.hidden, "heads": a.heads,
            "kv_heads": a.kv_heads, "dense_first_layers": 2, "kv_layout": a.layout, "rope": a.rope, "family": a.family,
-           "head_dim": a.head_dim, "intermediate": a.inter, "vocab": a.vocab,
+           "head_dim": a.head_dim, "intermediate": a.inter, "vocab": a.vocab, "dtype": a.dtype,
            "ms_per_token_quest": results["quest"], "ms_per_token_full_kv": results["dense"],
            "speedup": results["dense"] / results["quest"],
            "reference_published": "RTX 6000 Ada, ctx 32768 FP16: 36.8 ms -> 21.2 ms @ budget 2048 (1.74x)"}

@@ -132,6 +132,14 @@ int quest_append_kv_cache_prefill(const void* k, const void* v, uint32_t append_
  * decode_attn.cuh:1092-1149, kernel :245-401).
  * q: [1][num_qo_heads][head_dim]; o: [num_qo_heads][n_out] fp16 with n_out = (number of KV
  * pages) - 1; o[h][p] = fp16( sum_d max(q*Kmax, q*Kmin) ).
+ * Shapes: head_dim 64 / 128 / 256, group (num_qo_heads / kv heads) 1 / 2 / 4 / 8, any page size, the three layouts;
+ * QUEST_EUNSUPPORTED otherwise, before anything is launched and with `o` untouched.  REFUSED within that set, by every
+ * estimate entry (this one, quest_append_estimate, quest_estimate_attn_score_batched, quest_append_estimate_batched in
+ * both forms): head_dim 256 with group 8 on QUEST_LAYOUT_NHD_ROT when the number of kv heads is a multiple of 4 -- the
+ * rotation of such a pool (rot = 3) needs 4 kv heads in one workgroup tile, whose 32 query vectors of 256 elements do not
+ * fit the tile's staging pass.  The same shapes on QUEST_LAYOUT_NHD and QUEST_LAYOUT_HND are served (same scores bit for
+ * bit).  quest_estimate_plan (below, no GPU needed) answers for a shape what the launch would; the Python controllers ask
+ * it at construction.
  */
 int quest_estimate_attn_score(const void* q, void* o, uint32_t num_qo_heads, uint32_t n_out,
                               quest_paged_kv_t metadata, quest_stream_t stream);
@@ -587,6 +595,17 @@ int quest_decode_set_pages_per_chunk(quest_decode_handler_t* h, uint32_t pages_p
  * of the launch (q + k + v rows; 2 x intermediate for the gate/up launch).  The plan does not depend on the element
  * type: fp16 and bf16 are both 16 bits wide, so a launch of either type takes the kernel named here. */
 int quest_decode_batched_plan(uint32_t in_dim, uint32_t virtual_rows, uint32_t n_tokens, int rope, uint32_t info[6]);
+
+/* Which workgroup tile an estimate launch of this shape takes (tests / tuning / the controllers' early check; host function,
+ * no GPU, nothing is launched): 0 and info = {waves per workgroup (2 or 4), kv heads per tile (1, 2, 4 or 8), entries
+ * (pages) per tile}, or the code every estimate entry returns for the shape -- QUEST_EINVAL (unknown layout, zero heads,
+ * num_qo_heads not a multiple of num_kv_heads, info NULL), QUEST_EUNSUPPORTED (head_dim / group outside the built set, or a
+ * refused shape: see quest_estimate_attn_score).  tiles != 0: the tiles form of quest_append_estimate_batched
+ * (tile_max_offset != 0), whose tile must be a multiple of 8 entries wide.  It is the function the launch itself plans
+ * with.  A tile scores `entries` consecutive pages of `kv heads` heads; its page-table entry is one scalar load when the
+ * page size is a multiple of `entries`, else one load per row.  The plan does not depend on the element type. */
+int quest_estimate_plan(uint32_t head_dim, uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t layout, int tiles,
+                        uint32_t info[3]);
 
 #ifdef __cplusplus
 }

@@ -81,20 +81,58 @@ __global__ __launch_bounds__(EWV* kWave, QUEST_EST_MIN_WAVES) void estimate_kern
     estimate_kernel_body<bf16_t, D, G, HND, EWV>(QUEST_ESTIMATE_ARGS);
 }
 
-// Tile shape of a launch with EWV-wave workgroups: kv heads per tile (`hw`) and whether the shape can be served.
-template <int D, int G, int EWV>
-static bool estimate_tile_shape(const quest_paged_kv_t& meta, const AppendTail& tail, const PoolStrides& strides, uint32_t& hw) {
-    constexpr int R = kWave / (D / kVec);
-    constexpr uint32_t ROWS = EWV * est_iter<G>() * R;
-    hw = pick_tile_heads(meta.num_heads, G, D / kVec, EWV);
+// The launch planner: which kernel instantiation and tile a shape takes.  ONE function for the launch (launch_estimate) and
+// for quest_estimate_plan, which tests and the controllers ask without a GPU.
+struct EstimatePlan {
+    uint32_t waves;  // waves per workgroup (EWV): 2 or 4
+    uint32_t hw;     // kv heads per tile: 1, 2, 4 or 8
+    uint32_t ew;     // entries (pages) per tile = tile rows / hw
+};
+
+// Tile shape of a launch with `ewv`-wave workgroups: kv heads per tile (`hw`) and whether the shape can be served.
+static bool estimate_tile_shape(uint32_t D, uint32_t G, uint32_t ewv, uint32_t num_heads, uint32_t rot, bool tiles, uint32_t& hw) {
+    const uint32_t lpr = D / kVec, R = kWave / lpr;
+    const uint32_t rows = ewv * (uint32_t)(G >= 2 ? QUEST_EST_ITER_GQA : kEstIter) * R;  // est_iter<G>()
+    hw = pick_tile_heads(num_heads, G, lpr, ewv);
     // Tile maxima are one key per run of 8 consecutive columns of ONE query head, taken from 8 consecutive lanes of the
     // score store loop: a tile must be a multiple of 8 entries wide.  Narrow the tile's head range where it is not (head_dim
     // 256, two-wave workgroups), and refuse what still does not fit -- before anything is launched.
-    while (tail.tile_off && hw > 1 && (ROWS / hw) % 8u != 0) hw >>= 1;
-    if (tail.tile_off && (ROWS / hw) % 8u != 0) return false;
+    while (tiles && hw > 1 && (rows / hw) % 8u != 0) hw >>= 1;
+    if (tiles && (rows / hw) % 8u != 0) return false;
     // row-rotated pool: the heads of a tile's rows (slot ^ (entry & rot)) must be heads of the same tile
-    if (strides.rot >= hw) return false;
-    return hw * G * (D / kVec) <= 2u * EWV * kWave;  // q staging capacity
+    if (rot >= hw) return false;
+    return hw * G * lpr <= 2u * ewv * kWave;  // q staging capacity
+}
+
+// Workgroup width: TWO waves (32-row tiles) where the tile shape allows -- smaller workgroups start and retire in finer
+// steps, measured A B A B on one box (profiles/r06_ab_estimate_tile_shapes.txt, r06_ab_estimate_waves.txt): cfg 4 A+E 9.16 ->
+// 8.73 us (layer 28.9 -> 28.4), cfg 3 7.97 -> 7.83 (21.82 -> 21.72), 8 x cfg 3 two-launch form 11.20 -> 11.11, cfg 5 no
+// change; 8 waves and 8 load rounds per wave are slower -- else the four-wave tile of rounds 1-5 (it stages twice the query
+// vectors: GQA shapes whose group does not fit two waves' staging, row-rotated pools whose rotation needs >= 4 heads).
+// -DQUEST_EST_WAVES=4 forces the four-wave form (A/B).
+// QUEST_EUNSUPPORTED: a head_dim / group without an instantiation, or a shape neither width serves (the refused shapes
+// listed at quest_estimate_attn_score in include/quest_hip.h).
+static int estimate_plan(uint32_t D, uint32_t G, uint32_t num_heads, uint32_t layout, bool tiles, EstimatePlan& plan) {
+    if (D != 64 && D != 128 && D != 256) return QUEST_EUNSUPPORTED;
+    if (G != 1 && G != 2 && G != 4 && G != 8) return QUEST_EUNSUPPORTED;
+    quest_paged_kv_t shape{};
+    shape.num_heads = num_heads, shape.head_dim = D, shape.page_size = 1, shape.layout = layout;
+    const uint32_t rot = pool_strides(shape).rot;
+    for (uint32_t ewv = (kEstWaves == 2 ? 2u : 4u); ewv <= 4u; ewv += 2u) {
+        uint32_t hw = 0;
+        if (!estimate_tile_shape(D, G, ewv, num_heads, rot, tiles, hw)) continue;
+        const uint32_t rows = ewv * (uint32_t)(G >= 2 ? QUEST_EST_ITER_GQA : kEstIter) * (kWave / (D / kVec));
+        plan.waves = ewv, plan.hw = hw, plan.ew = rows / hw;
+        return 0;
+    }
+    return QUEST_EUNSUPPORTED;
+}
+
+// argument checks on the head counts and the layout, shared by every estimate entry and quest_estimate_plan
+static int estimate_check_heads(uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t layout) {
+    if (layout > QUEST_LAYOUT_NHD_ROT || num_kv_heads == 0) return QUEST_EINVAL;
+    if (num_qo_heads == 0 || num_qo_heads % num_kv_heads != 0) return QUEST_EINVAL;
+    return 0;
 }
 
 template <int D, int G, int EWV>
@@ -128,21 +166,14 @@ static int launch_estimate_w(const void* q, void* o, uint32_t n_out, const quest
     return 0;
 }
 
-// Workgroup width: TWO waves (32-row tiles) where the tile shape allows -- smaller workgroups start and retire in finer
-// steps, measured A B A B on one box (profiles/r06_ab_estimate_tile_shapes.txt, r06_ab_estimate_waves.txt): cfg 4 A+E 9.16 ->
-// 8.73 us (layer 28.9 -> 28.4), cfg 3 7.97 -> 7.83 (21.82 -> 21.72), 8 x cfg 3 two-launch form 11.20 -> 11.11, cfg 5 no
-// change; 8 waves and 8 load rounds per wave are slower -- else the four-wave tile of rounds 1-5 (it stages twice the query
-// vectors: GQA shapes whose group does not fit two waves' staging, row-rotated pools whose rotation needs >= 4 heads).
-// -DQUEST_EST_WAVES=4 forces the four-wave form (A/B).
+// the planner's choice (estimate_plan above) -> the instantiation
 template <int D, int G>
 static int launch_estimate(const void* q, void* o, uint32_t n_out, const quest_paged_kv_t& meta, const AppendTail& tail,
                            hipStream_t s, uint32_t n_seqs) {
-    const PoolStrides strides = pool_strides(meta);
-    uint32_t hw = 0;
-    if (kEstWaves == 2 && estimate_tile_shape<D, G, 2>(meta, tail, strides, hw))
-        return launch_estimate_w<D, G, 2>(q, o, n_out, meta, tail, s, n_seqs, hw);
-    if (estimate_tile_shape<D, G, 4>(meta, tail, strides, hw)) return launch_estimate_w<D, G, 4>(q, o, n_out, meta, tail, s, n_seqs, hw);
-    return QUEST_EUNSUPPORTED;
+    EstimatePlan plan{};
+    if (int e = estimate_plan(D, G, meta.num_heads, meta.layout, tail.tile_off != 0, plan)) return e;
+    if (plan.waves == 2) return launch_estimate_w<D, G, 2>(q, o, n_out, meta, tail, s, n_seqs, plan.hw);
+    return launch_estimate_w<D, G, 4>(q, o, n_out, meta, tail, s, n_seqs, plan.hw);
 }
 
 template <int D>
@@ -166,8 +197,8 @@ static int estimate_entry(const void* q, void* o, uint32_t num_qo_heads, uint32_
     // element type: the metadata view's, and the KV view's of a launch that also appends must agree with it
     if (int e = tail.enabled ? check_dtype_pair(tail.kv, metadata) : check_dtype(metadata)) return e;
     if (!q || !metadata.data || !metadata.indices) return QUEST_EINVAL;
-    if (metadata.layout > QUEST_LAYOUT_NHD_ROT || metadata.num_heads == 0 || metadata.page_size == 0) return QUEST_EINVAL;
-    if (num_qo_heads == 0 || num_qo_heads % metadata.num_heads != 0) return QUEST_EINVAL;
+    if (metadata.page_size == 0) return QUEST_EINVAL;
+    if (int e = estimate_check_heads(num_qo_heads, metadata.num_heads, metadata.layout)) return e;
     if (n_out > 0 && !o) return QUEST_EINVAL;
     if (n_out == 0 && !tail.enabled) return 0;  // nothing to score (single page)
     const uint32_t G = num_qo_heads / metadata.num_heads;
@@ -177,6 +208,16 @@ static int estimate_entry(const void* q, void* o, uint32_t num_qo_heads, uint32_
         case 256: return dispatch_group<256>(G, q, o, n_out, metadata, tail, s, n_seqs);
         default: return QUEST_EUNSUPPORTED;
     }
+}
+
+extern "C" int quest_estimate_plan(uint32_t head_dim, uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t layout, int tiles,
+                                   uint32_t info[3]) {
+    if (!info) return QUEST_EINVAL;
+    if (int e = estimate_check_heads(num_qo_heads, num_kv_heads, layout)) return e;
+    EstimatePlan plan{};
+    if (int e = estimate_plan(head_dim, num_qo_heads / num_kv_heads, num_kv_heads, layout, tiles != 0, plan)) return e;
+    info[0] = plan.waves, info[1] = plan.hw, info[2] = plan.ew;
+    return 0;
 }
 
 extern "C" int quest_estimate_attn_score(const void* q, void* o, uint32_t num_qo_heads, uint32_t n_out,

@@ -14,6 +14,7 @@ GQA pools (per-query-head selection).
 """
 from __future__ import annotations
 
+import ctypes
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -27,6 +28,7 @@ from .utils import TensorLayout
 # per sequence up take the tiles launches (tile maxima handed from the estimate to the attention launch); below, every
 # workgroup of a head selects over the whole row.  A controller's ``tiles_min_pages`` overrides it.
 TILES_MIN_PAGES = 4097
+QUEST_EUNSUPPORTED = -2  # include/quest_hip.h
 
 
 def _state_row(c: "InferenceController"):
@@ -34,6 +36,27 @@ def _state_row(c: "InferenceController"):
     kv, meta = c.kv_cache, c.metadata_cache
     return [kv.seqlen, len(kv.indicies), kv.last_page_len, kv.indicies[-1], len(meta.indicies), meta.last_page_len,
             meta.indicies[-1], 0]
+
+
+def _check_estimate_shape(num_heads: int, num_kv_heads: int, head_dim: int, layout: int) -> None:
+    """Refuse at construction a shape whose page-score estimate the library refuses on THIS pool layout and serves on
+    another one (``quest_estimate_plan``, include/quest_hip.h: head_dim 256 with 8 query heads per kv head on the
+    row-rotated pool when the kv heads are a multiple of 4) -- such a controller would build its pools and then fail inside
+    its first sparse decode step.  The tiles form is refused wherever the whole-row form is, so there is no other route.
+    Shapes no layout serves (a group or head_dim outside the built set) are left to the operators, as before: a controller
+    may still run full attention over them."""
+    from .._lib import lib
+
+    info = (ctypes.c_uint32 * 3)()
+    if lib.quest_estimate_plan(head_dim, num_heads, num_kv_heads, layout, 0, info) != QUEST_EUNSUPPORTED:
+        return
+    serving = [TensorLayout.FORMAT2STR[other] for other in sorted(TensorLayout.FORMAT2STR)
+               if other != layout and lib.quest_estimate_plan(head_dim, num_heads, num_kv_heads, other, 0, info) == 0]
+    if serving:
+        raise ValueError(
+            f"the page-score estimate does not serve {num_heads} query heads / {num_kv_heads} kv heads x head_dim {head_dim} "
+            f"on kv_layout {TensorLayout.FORMAT2STR[layout]} (whole rows or tiles form: QUEST_EUNSUPPORTED from "
+            f"quest_estimate_plan); layouts that serve this shape: {', '.join(serving)}")
 
 
 def _make_handler(layout: int, dtype):
@@ -78,6 +101,7 @@ class InferenceController:
         self.head_dim = head_dim
         self.page_size = page_size
         self.layout = TensorLayout.parse(layout)
+        _check_estimate_shape(self.num_heads, self.num_kv_heads, head_dim, self.layout)
         self.device = device
         self.dtype = dtype
 
@@ -271,6 +295,9 @@ class BatchedInferenceController:
         self.num_kv_heads = num_heads if num_kv_heads is None else num_kv_heads
         self.head_dim, self.page_size, self.device, self.dtype = head_dim, page_size, device, dtype
         self.layout = TensorLayout.parse(layout)
+        if self.num_heads % self.num_kv_heads != 0:
+            raise ValueError(f"num_heads {num_heads} is not a multiple of num_kv_heads {num_kv_heads}")
+        _check_estimate_shape(self.num_heads, self.num_kv_heads, head_dim, self.layout)  # before the shared pools exist
         self._page_budget = page_budget
         pages = (max_seq_len + page_size - 1) // page_size
         meta_pages = (pages + page_size - 1) // page_size

@@ -607,6 +607,42 @@ int quest_decode_batched_plan(uint32_t in_dim, uint32_t virtual_rows, uint32_t n
 int quest_estimate_plan(uint32_t head_dim, uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t layout, int tiles,
                         uint32_t info[3]);
 
+/*
+ * SIGN PLANES: a shadow store of ONE layer's metadata pool for ONE single-sequence MHA cache (EXTENSION).  With one query
+ * head per kv head the estimate needs, per (page, feature), max(Kslot, Vslot) where q >= 0 and min(Kslot, Vslot) where
+ * q < 0 -- one of the pool's two fp16 values.  The planes hold both, taken with the estimate kernel's packed fp16 max / min
+ * (so reversed slots, +-inf and NaN entries select what the pool launch selects), laid out
+ *     [kv head][block of 256 logical pages][feature][sign: 0 = max, 1 = min][256 pages]     (fp16)
+ * so that the pages of one (head, feature, sign) are contiguous in 512-byte runs and indexed by LOGICAL page: a launch reads
+ * the run of the sign it needs -- half the bytes, no page table.  plane_pages = the page capacity of the store, a multiple
+ * of 256 and >= every max_n_out it is used with; the buffer (16-byte aligned, caller-owned, contents arbitrary before the
+ * build) has quest_estimate_planes_bytes bytes.
+ * `covered` (one device int32 per layer, caller-owned, 0 = nothing) counts the leading logical pages whose plane entries
+ * equal the pool's.  Only the two launches below write it.  Whoever changes the metadata of a page below `covered` by other
+ * means (a cache set back to fewer pages, pool bytes rewritten) must lower it or build again.
+ * Shapes served: n_seqs 1, num_qo_heads == num_kv_heads, head_dim 128, page size 16 on the KV and the metadata pool, fp16,
+ * whole score rows (tile_max_offset 0) -- QUEST_EUNSUPPORTED otherwise, checked first and before anything is launched.
+ */
+uint64_t quest_estimate_planes_bytes(uint32_t num_kv_heads, uint32_t plane_pages);
+
+/* Transpose the metadata of the sequence's complete pages -- state->n_pages - 1, plus the last page when
+ * state->kv_last_page_len == kv_page_size; `state` must describe tokens that are in the pool -- into the planes and set
+ * *covered to their number.  About one pass over the layer's metadata; run it once per request after the prefill. */
+int quest_estimate_planes_build(void* planes, uint32_t plane_pages, int32_t* covered, quest_paged_kv_t metadata,
+                                uint32_t kv_page_size, const quest_step_state_t* state, quest_stream_t stream);
+
+/* quest_append_estimate_batched (whole rows) for the shapes above: same arguments, same score rows, same bits.  The append
+ * blocks run the same append; when the token completes its page they also write the page's entry into the planes at logical
+ * page n_pages - 1 and move *covered from n_pages - 1 to n_pages (never over a gap).  An estimate workgroup (kv head, 128
+ * pages) reads the planes when its scored pages all lie below *covered and its head's q has no zero or non-finite element,
+ * else the metadata pool -- so appends that do not maintain the planes (every other append entry) only leave *covered
+ * behind, and every sequence of calls gives the pool launch's scores. */
+int quest_append_estimate_planes_batched(const void* k, const void* v, quest_paged_kv_t kv, const void* q, void* o,
+                                         uint32_t num_qo_heads, uint32_t o_stride, uint32_t max_n_out,
+                                         uint32_t tile_max_offset, quest_paged_kv_t metadata,
+                                         const quest_step_state_t* state, quest_batch_t batch, void* planes,
+                                         uint32_t plane_pages, int32_t* covered, quest_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -587,6 +587,82 @@ def tiles_row_stride(max_n: int) -> int:
     return (tile_max_offset(max_n) + ((int(max_n) + 7) // 8 + 3) // 4 * 4 + 7) // 8 * 8
 
 
+# ---- sign planes (csrc/estimate_planes.hip, include/quest_hip.h SIGN PLANES): a single-sequence MHA controller registers
+# each layer's shadow store under the metadata layer's data pointer; ``append_estimate_batched(..., tiles=False)`` over that
+# layer, page table and step state then takes the planes launch -- whoever calls it (``decode_layer_dyn``, a benchmark that
+# times the launch on its own).  A registration is used only while the tensors it was made for are alive (weak references:
+# the allocator hands a dead controller's addresses to the next one), and only for the same table and state.
+
+PLANE_BLOCK = 256  # pages per workgroup of the planes launch: the page capacity of a store is a multiple of it
+_PLANES: dict = {}
+
+
+class _Planes:
+    __slots__ = ("meta_ref", "state_ref", "state_ptr", "table_ptr", "planes", "covered", "plane_pages")
+
+
+def plane_pages_for(max_pages: int) -> int:
+    """Page capacity of a planes store that serves a pool of ``max_pages`` pages: padded to whole page blocks."""
+    return (int(max_pages) + PLANE_BLOCK - 1) // PLANE_BLOCK * PLANE_BLOCK
+
+
+def estimate_planes_bytes(num_kv_heads: int, plane_pages: int) -> int:
+    return int(lib.quest_estimate_planes_bytes(int(num_kv_heads), int(plane_pages)))
+
+
+def estimate_planes_build(planes, plane_pages: int, covered, metadata_data, meta_table, state, kv_page_size: int,
+                          layout: int) -> None:
+    """Transpose the complete pages of one layer's metadata pool into ``planes`` (fp16, ``estimate_planes_bytes`` bytes)
+    and set ``covered`` (int32, one element) to their number, both read from ``state`` (``[8]`` or ``[1, 8]`` int32)."""
+    for t, n in ((planes, "planes"), (covered, "covered"), (metadata_data, "metadata_data"), (state, "state")):
+        _check_input(t, n)
+    _check_eq(covered.dtype, torch.int32, "covered.scalar_type(), torch::kInt32")
+    _check_eq(planes.dtype, torch.float16, "planes.scalar_type(), torch::kHalf")
+    meta = _paged(metadata_data, meta_table, None, 1, 0, layout)
+    _check_ge(planes.numel() * 2, estimate_planes_bytes(meta.num_heads, plane_pages), "planes bytes")
+    check(lib.quest_estimate_planes_build(planes.data_ptr(), int(plane_pages), covered.data_ptr(), meta, int(kv_page_size),
+                                          state.data_ptr(), _stream(planes)), "estimate_planes_build")
+
+
+def register_estimate_planes(metadata_data, meta_table, state, planes, covered, plane_pages: int) -> None:
+    """Route ``append_estimate_batched(..., tiles=False)`` over (``metadata_data``, ``meta_table``, ``state``) to the planes
+    launch with this store.  The caller keeps ``metadata_data`` and ``state`` alive for as long as it wants the route."""
+    import weakref
+
+    e = _Planes()
+    e.meta_ref, e.state_ref = weakref.ref(metadata_data), weakref.ref(state)
+    e.state_ptr, e.table_ptr = state.data_ptr(), meta_table.data_ptr()
+    e.planes, e.covered, e.plane_pages = planes, covered, int(plane_pages)
+    entries = [x for x in _PLANES.get(metadata_data.data_ptr(), ()) if _planes_alive(x) and x.state_ptr != e.state_ptr]
+    _PLANES[metadata_data.data_ptr()] = entries + [e]
+
+
+def unregister_estimate_planes(metadata_data, state=None) -> None:
+    """Drop the registration(s) under ``metadata_data`` (of ``state`` only, where given)."""
+    key = metadata_data.data_ptr()
+    left = [x for x in _PLANES.get(key, ()) if state is not None and x.state_ptr != state.data_ptr() and _planes_alive(x)]
+    if left:
+        _PLANES[key] = left
+    else:
+        _PLANES.pop(key, None)
+
+
+def _planes_alive(e) -> bool:
+    return e.meta_ref() is not None and e.state_ref() is not None
+
+
+def estimate_planes_for(metadata_data, meta_table, state):
+    """The registered store that serves this (metadata layer, page table, step state), or None."""
+    entries = _PLANES.get(metadata_data.data_ptr())
+    if not entries:
+        return None
+    for e in entries:
+        if e.state_ptr == state.data_ptr() and e.table_ptr == meta_table.data_ptr() and _planes_alive(e) \
+                and e.meta_ref().data_ptr() == metadata_data.data_ptr():
+            return e
+    return None
+
+
 def append_estimate_batched(k, v, kv_data, kv_tables, q, o, metadata_data, meta_tables, state, max_n_out: int,
                             layout: int, tiles: bool = False) -> bool:
     """append_estimate for ``n`` sequences in one launch, lengths / last-page ids / n_out read from ``state``: k/v
@@ -615,6 +691,15 @@ def append_estimate_batched(k, v, kv_data, kv_tables, q, o, metadata_data, meta_
     meta = _paged(metadata_data, meta_tables, None, 1, 0, layout)
     if tiles:
         _check_ge(o.size(2), tiles_row_stride(max_n_out), "o.size(2), tiles_row_stride(max_n_out)")
+    planes = None if tiles or not _PLANES or b.n_seqs != 1 else estimate_planes_for(metadata_data, meta_tables, state)
+    if planes is not None and planes.plane_pages >= max_n_out:
+        # a registered shadow store of this layer (sign planes): same rows, same bits, half the metadata bytes
+        check(lib.quest_append_estimate_planes_batched(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1),
+                                                       o.size(2), int(max_n_out), 0, meta, state.data_ptr(), b,
+                                                       planes.planes.data_ptr(), planes.plane_pages,
+                                                       planes.covered.data_ptr(), _stream(k)),
+              "append_estimate_planes_batched")
+        return True
     code = lib.quest_append_estimate_batched(k.data_ptr(), v.data_ptr(), kv, q.data_ptr(), o.data_ptr(), q.size(1), o.size(2),
                                              int(max_n_out), tile_max_offset(max_n_out) if tiles else 0, meta,
                                              state.data_ptr(), b, _stream(k))

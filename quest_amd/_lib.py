@@ -104,6 +104,10 @@ SIGNATURES = {
                                                  c_u32, c_vp]),
     "quest_decode_batched_plan": (ctypes.c_int, [c_u32, c_u32, c_u32, ctypes.c_int, c_vp]),
     "quest_estimate_plan": (ctypes.c_int, [c_u32, c_u32, c_u32, c_u32, ctypes.c_int, c_vp]),
+    "quest_estimate_planes_bytes": (ctypes.c_uint64, [c_u32, c_u32]),
+    "quest_estimate_planes_build": (ctypes.c_int, [c_vp, c_u32, c_vp, PagedKV, c_u32, c_vp, c_vp]),
+    "quest_append_estimate_planes_batched": (ctypes.c_int, [c_vp, c_vp, PagedKV, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, PagedKV,
+                                                             c_vp, Batch, c_vp, c_u32, c_vp, c_vp]),
     "quest_rms_norm_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_vp]),
     "quest_prefill_with_paged_kv_cache": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, PagedKV, c_u32, ctypes.c_int, c_vp]),
 }

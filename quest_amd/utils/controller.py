@@ -15,6 +15,7 @@ GQA pools (per-query-head selection).
 from __future__ import annotations
 
 import ctypes
+import os
 from typing import Dict, Optional, Tuple
 
 import torch
@@ -88,6 +89,11 @@ class InferenceController:
     one_launch_layers = False
     tiles_min_pages = TILES_MIN_PAGES
     dtype = torch.float16  # element type of pools, handlers, top-k buffers and score scratch; the constructor's argument
+    # sign planes for the sparse layers' estimate where the shape is eligible (estimate_planes_eligible); False = never
+    estimate_planes = True
+    _planes = _planes_covered = None
+    _planes_pages = 0
+    _planes_registered = False
 
     def __init__(self, num_layers, num_heads, head_dim, page_size,
                  page_budget,  # pages, including the last (current) page
@@ -239,9 +245,68 @@ class InferenceController:
         assert len(self.kv_cache.indicies) >= 1, "prefill first"
         self.inference_page_budget = min(self._page_budget, self.max_pages)
         _plan_graph_handlers(self, self.inference_page_budget, dense_layers)
+        self._build_estimate_planes()
+
+    # ------------------------------------------------------------------ sign planes (csrc/estimate_planes.hip)
+    def estimate_planes_eligible(self) -> bool:
+        """Whether the sparse layers of this controller read their page scores from sign planes: a shadow store of each
+        layer's metadata, per (kv head, feature, sign of q) contiguous over logical pages, of which the MHA estimate
+        fetches half.  One fp16 MHA sequence, head_dim 128, page size 16, a budget below the pool's
+        capacity (else every layer is dense), rows short of the tiles launches; ``estimate_planes = False`` or
+        QUEST_ESTIMATE_PLANES=0 switch it off."""
+        return bool(self.estimate_planes) and os.environ.get("QUEST_ESTIMATE_PLANES", "1") != "0" \
+            and self.n_seqs == 1 and self.num_heads == self.num_kv_heads and self.head_dim == 128 \
+            and self.page_size == 16 and self.dtype == torch.float16 and self.step_state is not None \
+            and self.inference_page_budget is not None and self.inference_page_budget < self.max_pages \
+            and self.max_pages - 1 < self.tiles_min_pages  # (longer rows take the tiles launches, which read the pool)
+
+    def _build_estimate_planes(self) -> None:
+        """Allocate the planes once, then per layer: transpose the complete pages' metadata into them (``covered`` = their
+        number) and register the store in ``_kernels``, whose append + estimate launch over this layer then takes it.  The
+        device state must describe tokens that are in the pools (after the prefill, between decode tokens)."""
+        from .. import _kernels
+
+        self._drop_estimate_planes()
+        if not self.estimate_planes_eligible():
+            return
+        layers = self.metadata_cache.pool.num_layers
+        pages = _kernels.plane_pages_for(self.max_pages)
+        halves = _kernels.estimate_planes_bytes(self.num_kv_heads, pages) // 2
+        if self._planes is None or tuple(self._planes.shape) != (layers, halves):
+            # ordinary tensors whatever mode the caller is in (a model's prefill runs under inference_mode, resets do not):
+            # only the kernels and the two in-place updates below ever write them
+            with torch.inference_mode(False):
+                self._planes = torch.empty((layers, halves), dtype=torch.float16, device=self.device)
+                self._planes_covered = torch.zeros(layers, dtype=torch.int32, device=self.device)
+        self._planes_pages = pages
+        for l in range(layers):
+            meta = self.metadata_layer(l)
+            _kernels.estimate_planes_build(self._planes[l], pages, self._planes_covered[l:l + 1], meta, self.meta_table_full,
+                                           self.step_state, self.page_size, self.layout)
+            _kernels.register_estimate_planes(meta, self.meta_table_full, self.step_state, self._planes[l],
+                                              self._planes_covered[l:l + 1], pages)
+        self._planes_registered = True
+
+    def _drop_estimate_planes(self) -> None:
+        """Zero ``covered`` and drop the registrations: the next launches read the metadata pool."""
+        if not self._planes_registered:
+            return
+        from .. import _kernels
+
+        self._planes_registered = False
+        with torch.inference_mode():  # (an in-place update is allowed there for every kind of tensor)
+            self._planes_covered.zero_()
+        for l in range(self.metadata_cache.pool.num_layers):
+            _kernels.unregister_estimate_planes(self.metadata_layer(l), self.step_state)
 
     def sync_device_state(self) -> None:
         self.step_state.copy_(torch.tensor(_state_row(self), dtype=torch.int32))
+        if self._planes_registered:
+            # the cache may have been set back: the mirror's last page and everything behind it are no longer vouched for
+            # (the mirror may run one reserved token ahead, so a last page that looks full may still lack its token; a
+            # planes launch that completes a page writes its entries again and counts on from there)
+            with torch.inference_mode():
+                self._planes_covered.clamp_(max=len(self.kv_cache.indicies) - 1)
 
     def kv_layer(self, layer_idx: int) -> torch.Tensor:
         return self.kv_cache.buf_layer(layer_idx)
@@ -264,6 +329,7 @@ class InferenceController:
         self.invalidate_device_state()
 
     def invalidate_device_state(self) -> None:
+        self._drop_estimate_planes()  # covered = 0, registrations dropped: the store says nothing about the next request
         self.kv_table_full = self.meta_table_full = self.step_state = None
         self.kv_tables = self.meta_tables = self.step_states = None
         self.state_epoch += 1  # graphs captured before this call are stale

@@ -330,6 +330,43 @@ int quest_decode_forward_fused_topk_batched(quest_decode_handler_t* h, const voi
  * of 8) -- the caller then issues the whole-row form.  quest_decode_last_launch_info reports front-end variant 8 and n_seqs.
  */
 
+/*
+ * GROUP-SHARED PAGE SELECTION for GQA (EXTENSION, opt-in): ONE selection per KV HEAD, attended by all query heads of its
+ * group, in place of quest_decode_forward_fused_topk_batched's one selection per query head.  The attention launch then
+ * fetches each selected K/V tile once per kv head instead of once per query head (group x fewer K/V bytes).  This is NOT the
+ * reference's algorithm -- evaluation/quest_attention.py:139-140 repeats K/V and selects per query head -- so nothing takes
+ * it by default, and its effect on a real checkpoint's accuracy has not been measured.
+ *
+ * Semantics, for sequence i and kv head hk, G = num_qo_heads / num_kv_heads:
+ *   1. group score of page p = the maximum over g < G of scores[i][hk * G + g][p] (the rows quest_append_estimate_batched
+ *      writes), taken on the 16-bit order-preserving keys the top-k uses: exact and total, also for +-0 and NaN patterns;
+ *   2. selection = the contract of the top-k operator on that row: k = min(budget_i - 1, n_pages_i - 1) columns, every key
+ *      above the threshold plus the lowest columns among ties, in ascending column order;
+ *   3. every head of the group attends those k pages + the current page; partial records, merge and lse as in the other
+ *      launches.
+ * For G = 1 the selection is quest_decode_forward_fused_topk_batched's, bit for bit.
+ *
+ * Arguments as quest_decode_forward_fused_topk_batched, without the tiles form.  state == NULL: the eager single-sequence
+ * form -- batch.n_seqs must be 1, the row length is max_n_scores, the current page comes from the view (last_page_len /
+ * last_page_idx) and the plan's selected-page count must not exceed max_n_scores.  begin_forward plans this launch's own
+ * work split of (kv head, chunk) workgroups next to the per-head one (at most 256 pages per workgroup) and sizes the
+ * workspace for both.  quest_decode_set_selection_out is served with rows [n_seqs][num_kv_heads][n_selected_pages of the
+ * plan]; quest_decode_last_launch_info reports front-end variant 9; an armed step advance rides in the merge launch.
+ * Return codes, all before anything is launched (o untouched): QUEST_EINVAL / QUEST_ESTATE as the sibling entry, and
+ * QUEST_EINVAL for state == NULL with n_seqs != 1; QUEST_ETOOLARGE for rows beyond QUEST_TOPK_MAX_ROW;
+ * QUEST_EUNSUPPORTED outside the envelope: page size 16, head_dim 64 / 128, group 1 / 2 / 4 / 8, at most
+ * QUEST_GROUP_TOPK_MAX_SELECTED selected pages, score rows of at most QUEST_GROUP_TOPK_MAX_ROW pages (each thread of the
+ * 512 keeps its 8 columns' keys and page ids in registers; longer rows would need the tiles form, not built for this
+ * launch), at most QUEST_GROUP_TOPK_MAX_SEQS sequences.
+ */
+#define QUEST_GROUP_TOPK_MAX_ROW 4096u
+#define QUEST_GROUP_TOPK_MAX_SELECTED 256u
+#define QUEST_GROUP_TOPK_MAX_SEQS 64u
+int quest_decode_forward_group_topk(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t paged_kv,
+                                    uint32_t num_qo_heads, const void* scores, uint32_t score_stride,
+                                    uint32_t max_n_scores, const quest_step_state_t* state, quest_batch_t batch, float* lse,
+                                    quest_stream_t stream);
+
 /* quest_append_kv_cache_decode with lengths / last-page ids from `state` (dense layers of a replayed step). */
 int quest_append_kv_cache_decode_batched(const void* k, const void* v, quest_paged_kv_t kv, quest_paged_kv_t metadata,
                                          const quest_step_state_t* state, quest_batch_t batch, quest_stream_t stream);

@@ -1030,6 +1030,44 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
         """``forward_fused_topk_batched`` under its single-sequence name: ``scores`` ``[Hq, stride]``, state ``[8]``."""
         return self.forward_fused_topk_batched(q, o, paged_kv_data, page_table, scores, state, max_n_scores, tiles=tiles)
 
+    def forward_group_topk(self, q, o, paged_kv_data, kv_tables, scores, state, max_n_scores: int, budgets=None,
+                           paged_kv_last_page_len: int = 1, paged_kv_last_page_idx: int = 0) -> bool:
+        """EXTENSION, opt-in: group-shared page selection for GQA -- ONE selection per kv head (the key-max of its group's
+        score rows, then the top-k contract), attended by all query heads of the group: each selected K/V tile is fetched
+        once per kv head.  Arguments as ``forward_fused_topk_batched``; ``state=None`` is the eager single-sequence form
+        (q/o ``[1, Hq, D]``, scores ``[Hq, stride]`` with ``max_n_scores`` live columns, ``kv_tables`` the page table
+        ``[max_n_scores + 1]``, the current page from ``paged_kv_last_page_len`` / ``paged_kv_last_page_idx``).
+        ``set_selection_out`` rows are ``[n_seqs, Hkv, n_selected]``.  Returns False (nothing launched, ``o`` untouched) where
+        the shape is outside the launch's envelope (page size 16, head_dim 64 / 128, group 1 / 2 / 4 / 8, <= 256 selected
+        pages, rows <= 4096 pages, <= 64 sequences)."""
+        for t, n in ((q, "q"), (o, "o"), (paged_kv_data, "paged_kv_data")):
+            _check_input(t, n)
+        if scores.dim() == 2:  # one sequence: rows possibly padded (decode_append_estimate's output)
+            _check_rows(scores, "scores")
+        else:
+            _check_input(scores, "scores")
+        scores = _lead(scores, 3)
+        _check_dim(3, q, "q")
+        _check_dim(3, scores, "scores")
+        if state is None:
+            _check_input(kv_tables, "kv_tables")
+            _check_eq(q.size(0), 1, "q.size(0), 1")
+            _check_ge(kv_tables.numel(), max_n_scores + 1, "kv_tables.numel(), max_n_scores + 1")
+            _check_eq(kv_tables.dtype, torch.int32, "kv_tables.scalar_type(), torch::kInt32")
+            b = Batch(1, 0, 0, 0, None)
+        else:
+            _check_input(state, "state")
+            b = _batch(state, kv_tables, None, budgets)
+        _check_eq(q.size(0), b.n_seqs, "q.size(0), n_seqs")
+        _check_eq(scores.size(0), b.n_seqs, "scores.size(0), n_seqs")
+        _check_eq(scores.size(1), q.size(1), "scores.size(1), num_qo_heads")
+        _check_ge(scores.stride(1), max_n_scores, "scores.stride(1), max_n_scores")
+        self._check_dtype(q, o, paged_kv_data, scores)
+        kv = _paged(paged_kv_data, kv_tables, None, paged_kv_last_page_len, paged_kv_last_page_idx, self._layout)
+        return _launched(lib.quest_decode_forward_group_topk(
+            self._h, q.data_ptr(), o.data_ptr(), kv, q.size(1), scores.data_ptr(), scores.stride(1), int(max_n_scores),
+            state.data_ptr() if state is not None else None, b, self._lse(q), _stream(q)), "BatchDecodeWithPagedKVCache")
+
     def layer_fused_batched(self, k, v, metadata_data, meta_tables, q, o, paged_kv_data, kv_tables, state,
                             max_n_scores: int, budgets=None, scores_out=None) -> bool:
         """One launch per layer of a batched step: ``append_estimate_batched`` + ``forward_fused_topk_batched`` as one
@@ -1072,7 +1110,8 @@ class BatchDecodeWithPagedKVCachePyTorchWrapper:
     def last_launch_info(self) -> dict:
         """Which kernel instantiation the handler's most recent per-head-list launch took: keys per thread of the fused
         front end (0 = index-tensor launch), waves per workgroup, front-end variant (DecodeParams.vec_front: 0 / 1 / 3
-        first generation staged / vector-staged / direct, 2 second generation, 8 tiles, 7 the one-launch layer), whether
+        first generation staged / vector-staged / direct, 2 second generation, 8 tiles, 7 the one-launch layer, 9 the
+        group-selection launch, whose workgroups are counted per kv head), whether
         the one-variant instantiation was launched, workgroups per head, sequences.  So that tests and benches can assert
         they run the same kernel."""
         info = (ctypes.c_uint32 * 6)()

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "decode_kernels.cuh"
+#include "group_topk_kernels.cuh"
 #include "pool_check.h"
 
 using namespace quest;
@@ -44,6 +45,7 @@ struct quest_decode_handler {
     std::vector<float*> retired_ws;
     uint32_t dec_waves = 4;
     uint32_t shared_ppc = 0, shared_chunks = 0;  // plan of the group-shared kernel (grid.y = kv heads)
+    uint32_t group_ppc = 0, group_chunks = 0;    // plan of the group-selection launch (grid.y = kv heads, fused front end)
     uint32_t batch = 1;                          // sequences per launch the plan / workspace are made for
     uint32_t num_cus = 256;                      // compute units of the current device (MI355X: 256)
     bool skip_merge = false;                     // measurement aid: leave the partial states unmerged
@@ -191,8 +193,13 @@ extern "C" int quest_decode_begin_forward(quest_decode_handler_t* h, uint32_t n_
     // the group-shared kernel runs one workgroup per (chunk, KV head): plan it for the same 512 workgroups
     h->shared_ppc = split_pages(n_slots, 2 * h->num_cus / (num_kv_heads * h->batch), h->forced_ppc, n_slots);
     h->shared_chunks = (n_slots + h->shared_ppc - 1) / h->shared_ppc;
+    // the group-selection launch (quest_decode_forward_group_topk): (chunk, kv head) workgroups for the same target as the
+    // per-head plan, each staging its chunk's page ids in LDS like the fused front end
+    h->group_ppc = split_pages(n_slots, target_workgroups(h) / (num_kv_heads * h->batch), h->forced_ppc, kFusedMaxPpc);
+    h->group_chunks = (n_slots + h->group_ppc - 1) / h->group_ppc;
     h->ws_stride = (head_dim + 2 + 31) / 32 * 32;
-    const uint32_t max_chunks = h->n_chunks > h->shared_chunks ? h->n_chunks : h->shared_chunks;
+    uint32_t max_chunks = h->n_chunks > h->shared_chunks ? h->n_chunks : h->shared_chunks;
+    if (h->group_chunks > max_chunks) max_chunks = h->group_chunks;
     const size_t need = (size_t)h->batch * num_qo_heads * max_chunks * h->ws_stride * sizeof(float);
 #ifdef QUEST_WALLSTAMPS
     const bool want_ws = true;  // one-chunk plans leave their per-workgroup stamps in the workspace as well
@@ -702,6 +709,69 @@ extern "C" int quest_decode_forward_fused_topk_batched(quest_decode_handler_t* h
     r.state = state, r.batch = batch;
     r.scores = scores, r.n_scores = max_n_scores, r.score_stride = score_stride, r.tile_off = tile_max_offset;
     return decode_entry(h, r, (hipStream_t)stream);
+}
+
+// ---- group-shared page selection (opt-in): one selection per kv head, attended by all heads of its group
+template <int D>
+static int launch_group_topk(quest_decode_handler* h, const GroupTopkParams& p, uint32_t gs, uint32_t n_seqs, hipStream_t s) {
+    const bool bf16 = h->dtype == QUEST_DTYPE_BF16;
+    constexpr int NW = kGroupTopkWaves;
+    dim3 grid(p.n_chunks, p.num_kv_heads, n_seqs), block(NW * kWave);
+#define QUEST_GROUP_CASE(GS)                                                                                                    \
+    case GS:                                                                                                                    \
+        hipLaunchKernelGGL((bf16 ? group_topk_attend_kernel_bfloat16<D, GS, NW> : group_topk_attend_kernel<D, GS, NW>), grid, block, 0, s, p); \
+        break;
+    switch (gs) {
+        QUEST_GROUP_CASE(1)
+        QUEST_GROUP_CASE(2)
+        QUEST_GROUP_CASE(4)
+        QUEST_GROUP_CASE(8)
+        default: return QUEST_EUNSUPPORTED;
+    }
+#undef QUEST_GROUP_CASE
+    QUEST_LAUNCH_CHECK();
+    uint32_t* info = h->last_launch;  // front-end variant 9 = the group-selection launch
+    info[0] = (uint32_t)kGroupTopkKeys, info[1] = (uint32_t)NW, info[2] = 9u, info[3] = 1u, info[4] = p.n_chunks, info[5] = n_seqs;
+    DecodeParams m{};  // what the merge launch reads
+    m.o = p.o, m.ws = p.ws, m.n_chunks = p.n_chunks, m.ws_stride = p.ws_stride;
+    return merge_and_advance<D>(h, m, p.num_kv_heads * gs * n_seqs, p.lse, s, bf16);
+}
+
+extern "C" int quest_decode_forward_group_topk(quest_decode_handler_t* h, const void* q, void* o, quest_paged_kv_t kv,
+                                               uint32_t num_qo_heads, const void* scores, uint32_t score_stride,
+                                               uint32_t max_n_scores, const quest_step_state_t* state, quest_batch_t batch,
+                                               float* lse, quest_stream_t stream) {
+    if (!scores || score_stride < max_n_scores) return QUEST_EINVAL;
+    if (!state && batch.n_seqs != 1) return QUEST_EINVAL;  // the eager form is one sequence: lengths come from the view
+    if (batch.n_seqs > 1 && batch.kv_table_stride < max_n_scores + 1) return QUEST_EINVAL;
+    DecodeRequest r = attention_request(q, o, kv, num_qo_heads, lse);
+    r.state = state, r.batch = batch;
+    r.scores = scores, r.n_scores = max_n_scores, r.score_stride = score_stride;
+    if (int e = check_request(h, r, Route::kHeadLists)) return e;
+    // the envelope (include/quest_hip.h), before anything is launched
+    const uint32_t group = num_qo_heads / kv.num_heads;
+    if (kv.page_size != 16 || (kv.head_dim != 64 && kv.head_dim != 128)) return QUEST_EUNSUPPORTED;
+    if (group != 1 && group != 2 && group != 4 && group != 8) return QUEST_EUNSUPPORTED;
+    if (h->n_sel > QUEST_GROUP_TOPK_MAX_SELECTED || max_n_scores > QUEST_GROUP_TOPK_MAX_ROW ||
+        batch.n_seqs > QUEST_GROUP_TOPK_MAX_SEQS || h->group_ppc > (uint32_t)kFusedMaxPpc)
+        return QUEST_EUNSUPPORTED;
+    GroupTopkParams p{};
+    p.q = (const half_t*)q, p.kv = (const half_t*)kv.data, p.tables = kv.indices, p.scores = (const uint16_t*)scores;
+    p.state = state, p.budgets = state ? batch.page_budgets : nullptr;
+    p.o = (half_t*)o, p.ws = h->ws, p.lse = lse;
+    p.sel_val_out = (uint16_t*)h->sel_val_out, p.sel_idx_out = h->sel_idx_out, p.sel_stride = h->n_sel;
+    p.st = pool_strides(kv), p.num_kv_heads = kv.num_heads;
+    p.n_cap = max_n_scores, p.score_stride = score_stride, p.table_stride = batch.kv_table_stride;
+    const uint32_t nt = kGroupTopkWaves * kWave, per_thread = (max_n_scores + nt - 1) / nt;
+    p.cpt = (per_thread + 3) / 4 * 4;  // 4 or 8: a thread's columns are one or two 8-byte loads per score row
+    p.vec_scores = ((uintptr_t)scores & 7u) == 0 && score_stride % 4u == 0 && score_stride >= ((max_n_scores + 3u) & ~3u) ? 1u : 0u;
+    p.table_vec = ((uintptr_t)kv.indices & 15u) == 0 && (batch.n_seqs == 1 || batch.kv_table_stride % 4u == 0) ? 1u : 0u;
+    p.n_sel = h->n_sel, p.n_scores = max_n_scores;
+    p.last_page_len = r.kv.last_page_len, p.last_page_idx = kv.last_page_idx;
+    p.pages_per_chunk = h->group_ppc, p.n_chunks = h->group_chunks, p.ws_stride = h->ws_stride;
+    p.scale_log2 = softmax_scale_log2(kv.head_dim);
+    return kv.head_dim == 64 ? launch_group_topk<64>(h, p, group, batch.n_seqs, (hipStream_t)stream)
+                             : launch_group_topk<128>(h, p, group, batch.n_seqs, (hipStream_t)stream);
 }
 
 // append + estimate + top-k + sparse attention of one layer for a whole batch in ONE launch (layer_device.cuh).

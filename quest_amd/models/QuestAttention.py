@@ -119,6 +119,22 @@ class QuestAttention(nn.Module):
             nvtx.range_push("full_attn")
             attn = qutils.decode_sparse_attn(q, iController, self.layer_idx, iController.kv_indices_without_last)
             nvtx.range_pop()
+        elif iController.group_selection:
+            # opt-in group-shared selection with the existing operators: key-max over the group, top-k on the kv heads'
+            # rows, attention with every row repeated for its group (the same pages as the group-selection launch)
+            nvtx.range_push("append_kv+estimate")
+            if self.fused:
+                scores = qutils.decode_append_estimate(q, k, v, iController, self.layer_idx)
+            else:
+                qutils.append_kv(k, v, iController, self.layer_idx)
+                scores = qutils.decode_estimate(q, iController, self.layer_idx)
+            nvtx.range_pop()
+            nvtx.range_push("group_topk")
+            pages = qutils.decode_group_topk(scores, iController)
+            nvtx.range_pop()
+            nvtx.range_push("approx_attn")
+            attn = qutils.decode_sparse_attn(q, iController, self.layer_idx, pages)
+            nvtx.range_pop()
         elif self.fused:
             nvtx.range_push("append_kv+estimate")
             scores = qutils.decode_append_estimate(q, k, v, iController, self.layer_idx)

@@ -32,6 +32,9 @@ __all__ = [
     # extensions (fused launches; same results as the op pairs they replace)
     "decode_append_estimate",
     "decode_topk_sparse_attn",
+    # group-shared page selection (opt-in, InferenceController(group_selection=True)) with the existing operators
+    "group_max_scores",
+    "decode_group_topk",
     # state-driven forms for hipGraph replay across tokens
     "step_advance_dyn",
     "score_scratch",
@@ -186,6 +189,34 @@ def decode_topk_sparse_attn(q: torch.Tensor, estimated_attn_score: torch.Tensor,
     return o
 
 
+# ---------------------------------------------------------------------------- group-shared selection, eager
+# ``InferenceController(group_selection=True)``: one page selection per kv head.  The captured / state-driven step takes
+# the group-selection launch (``_decode_layer``); the eager module path states the same selection with the existing
+# operators -- a key-max over the group, ``topk_filtering`` on ``num_kv_heads`` rows, ``forward`` with every row repeated
+# for its group -- and picks the same pages, bit for bit.
+
+def group_max_scores(estimated_attn_score: torch.Tensor, group: int) -> torch.Tensor:
+    """``[Hq, n]`` page scores -> ``[Hq / group, n]``: per kv head and page the largest score of the group's heads, the
+    maximum taken on the 16-bit order-preserving keys of the top-k (so exact and total, also for +-0 and NaN patterns)."""
+    bits = estimated_attn_score.contiguous().view(torch.int16).to(torch.int32) & 0xFFFF
+    keys = torch.where((bits & 0x8000) != 0, ~bits & 0xFFFF, bits | 0x8000)
+    keys = keys.view(-1, group, keys.size(-1)).amax(dim=1)
+    bits = torch.where((keys & 0x8000) != 0, keys & 0x7FFF, ~keys & 0xFFFF)
+    bits = torch.where(bits >= 0x8000, bits - 0x10000, bits).to(torch.int16)
+    return bits.view(estimated_attn_score.dtype)
+
+
+def decode_group_topk(estimated_attn_score: torch.Tensor, iController: InferenceController) -> torch.Tensor:
+    """Group-shared ``decode_topk``: the ``budget - 1`` best pages per KV head under the group score, into the first
+    ``num_kv_heads`` rows of ``topk_dout_buffer`` / ``topk_dindices_buffer``; returns the page ids with every row repeated
+    for its group, ``[Hq, budget - 1]`` -- the ``topk_indices`` of ``decode_sparse_attn``."""
+    c = iController
+    hk, group = c.num_kv_heads, c.num_heads // c.num_kv_heads
+    _kernels.topk_filtering(group_max_scores(estimated_attn_score, group), c.kv_indices_without_last[:hk],
+                            c.topk_dout_buffer[:hk], c.topk_dindices_buffer[:hk], c.topk_buf[:hk], c.inference_page_budget - 1)
+    return c.topk_dindices_buffer[:hk].repeat_interleave(group, dim=0)
+
+
 # ---------------------------------------------------------------------------- graph-replayable step
 # With ``iController.enable_device_state()`` the per-token quantities live in device memory; a step built
 # from the two calls below can be captured once (torch.cuda.graph) and replayed for every new token:
@@ -258,6 +289,18 @@ def _decode_layer(q, k, v, ctl, layer_idx, scores, rope_scale, rope_theta, apply
     max_n = ctl.max_pages - 1
     kvb, mb = ctl.kv_layer(layer_idx), ctl.metadata_layer(layer_idx)
     o = torch.empty_like(q) if out is None else out
+    if ctl.group_selection:
+        # opt-in: the unchanged append+estimate launch, then ONE selection per kv head and its gather in the
+        # group-selection launch (no one-launch layer, no tiles pair; no fall back to per-head selection)
+        if one_launch:
+            raise RuntimeError("the one-launch layer selects per query head: not available with group_selection=True")
+        _kernels.append_estimate_batched(k, v, kvb, ctl.kv_tables, q, scores, mb, ctl.meta_tables, ctl.step_states, max_n,
+                                         ctl.layout)
+        if not handler.forward_group_topk(q, o, kvb, ctl.kv_tables, scores, ctl.step_states, max_n, ctl.page_budgets):
+            raise RuntimeError("the group-selection launch does not serve this plan / shape (page_size 16, head_dim 64 / "
+                               "128, group 1 / 2 / 4 / 8, <= 256 selected pages, rows <= 4096 pages, <= 64 sequences)")
+        ctl.last_layer_launches = 2
+        return o
     if (ctl.one_launch_layers if one_launch is None else one_launch):
         if handler.layer_fused_batched(k, v, mb, ctl.meta_tables, q, o, kvb, ctl.kv_tables, ctl.step_states, max_n,
                                        ctl.page_budgets, scores if write_scores else None):

@@ -60,6 +60,35 @@ def _check_estimate_shape(num_heads: int, num_kv_heads: int, head_dim: int, layo
             f"quest_estimate_plan); layouts that serve this shape: {', '.join(serving)}")
 
 
+# the envelope of the group-selection launch (quest_decode_forward_group_topk, include/quest_hip.h)
+GROUP_TOPK_MAX_ROW, GROUP_TOPK_MAX_SELECTED, GROUP_TOPK_MAX_SEQS = 4096, 256, 64
+
+
+def _check_group_selection(num_heads: int, num_kv_heads: int, head_dim: int, page_size: int, page_budget: int,
+                           max_seq_len: int, n_seqs: int = 1) -> None:
+    """Refuse at construction a ``group_selection=True`` controller whose shape the group-selection launch does not serve.
+    There is no silent fall back to per-head selection: that would change which pages a model attends."""
+    group = num_heads // num_kv_heads
+    pages = (max_seq_len + page_size - 1) // page_size
+    why = None
+    if page_size != 16:
+        why = f"page_size {page_size} (the launch serves page size 16)"
+    elif head_dim not in (64, 128):
+        why = f"head_dim {head_dim} (the launch serves head_dim 64 and 128)"
+    elif group not in (1, 2, 4, 8):
+        why = f"{group} query heads per kv head (the launch serves groups of 1, 2, 4 and 8)"
+    elif page_budget - 1 > GROUP_TOPK_MAX_SELECTED:
+        why = (f"a budget of {page_budget} pages (the launch selects at most {GROUP_TOPK_MAX_SELECTED} pages besides the "
+               "current one)")
+    elif pages - 1 > GROUP_TOPK_MAX_ROW:
+        why = (f"a pool of {pages} pages per sequence (the launch serves score rows of at most {GROUP_TOPK_MAX_ROW} pages: "
+               f"max_seq_len <= {(GROUP_TOPK_MAX_ROW + 1) * page_size} tokens)")
+    elif n_seqs > GROUP_TOPK_MAX_SEQS:
+        why = f"{n_seqs} sequences (the launch serves at most {GROUP_TOPK_MAX_SEQS})"
+    if why:
+        raise ValueError(f"group_selection=True does not serve {why}")
+
+
 def _make_handler(layout: int, dtype):
     """A decode handler for pools of ``layout`` and ``dtype``: built the reference's way (fp16) unless the controller is
     bf16, which is the handler's explicit extension."""
@@ -91,6 +120,9 @@ class InferenceController:
     dtype = torch.float16  # element type of pools, handlers, top-k buffers and score scratch; the constructor's argument
     # sign planes for the sparse layers' estimate where the shape is eligible (estimate_planes_eligible); False = never
     estimate_planes = True
+    # opt-in: ONE page selection per kv head (the key-max of its group's scores), attended by all heads of the group
+    # (quest_decode_forward_group_topk); the default is the reference's selection per query head
+    group_selection = False
     _planes = _planes_covered = None
     _planes_pages = 0
     _planes_registered = False
@@ -99,7 +131,7 @@ class InferenceController:
                  page_budget,  # pages, including the last (current) page
                  max_seq_len,  # capacity of the KV / metadata pools, in tokens
                  dtype, device, num_kv_heads: Optional[int] = None, layout: int = TensorLayout.NHD,
-                 shuffle_seed: Optional[int] = None, kv_pool=None, metadata_pool=None):
+                 shuffle_seed: Optional[int] = None, kv_pool=None, metadata_pool=None, group_selection: bool = False):
         self.num_heads = num_heads
         self.num_kv_heads = num_heads if num_kv_heads is None else num_kv_heads
         if self.num_heads % self.num_kv_heads != 0:
@@ -108,6 +140,9 @@ class InferenceController:
         self.page_size = page_size
         self.layout = TensorLayout.parse(layout)
         _check_estimate_shape(self.num_heads, self.num_kv_heads, head_dim, self.layout)
+        self.group_selection = bool(group_selection)
+        if self.group_selection:
+            _check_group_selection(self.num_heads, self.num_kv_heads, head_dim, page_size, page_budget, max_seq_len)
         self.device = device
         self.dtype = dtype
 
@@ -351,7 +386,7 @@ class BatchedInferenceController:
 
     def __init__(self, n_seqs, num_layers, num_heads, head_dim, page_size, page_budget, max_seq_len, dtype, device,
                  num_kv_heads: Optional[int] = None, layout: int = TensorLayout.NHD,
-                 shuffle_seed: Optional[int] = None):
+                 shuffle_seed: Optional[int] = None, group_selection: bool = False):
         from .kv_cache import KvPool
 
         if n_seqs <= 0:
@@ -364,6 +399,9 @@ class BatchedInferenceController:
         if self.num_heads % self.num_kv_heads != 0:
             raise ValueError(f"num_heads {num_heads} is not a multiple of num_kv_heads {num_kv_heads}")
         _check_estimate_shape(self.num_heads, self.num_kv_heads, head_dim, self.layout)  # before the shared pools exist
+        self.group_selection = bool(group_selection)  # InferenceController.group_selection, for every sequence
+        if self.group_selection:
+            _check_group_selection(self.num_heads, self.num_kv_heads, head_dim, page_size, page_budget, max_seq_len, n_seqs)
         self._page_budget = page_budget
         pages = (max_seq_len + page_size - 1) // page_size
         meta_pages = (pages + page_size - 1) // page_size
@@ -373,7 +411,8 @@ class BatchedInferenceController:
                                     device, self.layout, None if shuffle_seed is None else shuffle_seed + 1)
         self.seqs = [InferenceController(num_layers, num_heads, head_dim, page_size, page_budget, max_seq_len, dtype,
                                          device, num_kv_heads=num_kv_heads, layout=layout, kv_pool=self.kv_pool,
-                                         metadata_pool=self.metadata_pool) for _ in range(n_seqs)]
+                                         metadata_pool=self.metadata_pool, group_selection=group_selection)
+                     for _ in range(n_seqs)]
         self._decode_handler = _make_handler(self.layout, dtype)
         self._dense_handler = None
         self.kv_tables = self.meta_tables = self.step_states = None

@@ -680,6 +680,64 @@ int quest_append_estimate_planes_batched(const void* k, const void* v, quest_pag
                                          const quest_step_state_t* state, quest_batch_t batch, void* planes,
                                          uint32_t plane_pages, int32_t* covered, quest_stream_t stream);
 
+/*
+ * Token sampling on the device (EXTENSION; opt-in): the token choice that follows the lm_head launch, so that a captured
+ * decode step needs no host round trip per token.  The reference samples on the host (the temperature / top-p / top-k
+ * sampler with a stop token of its scripts/example_demo.py, model.generate of transformers elsewhere).
+ *
+ * THE CONTRACT, per row i (one row = one sequence); tests/_sampling_ref.py restates it in float64.
+ *   Inputs: logits s[0..vocab) in the stored type (fp16 / bf16, converted exactly), temperature[i] (fp32), top_k[i] (int32),
+ *   top_p[i] (fp32), seed[i] (uint64) and the position pos_i = the index the sampled token will occupy: states[i].seq_len
+ *   (at the end of a state-driven step the state counts the token being decoded) or positions[i].
+ *   Order: tokens are ordered by (16-bit key descending, token index ascending); the key is the monotone key of the page
+ *   selection (sign-magnitude bits twiddled into an unsigned order; the same bit trick for bf16), so -0 < +0.
+ *   Greedy rows: temperature == 0 (and any temperature that is not a positive finite number), a row that holds a NaN or
+ *   +inf, a row whose maximum is -inf.  The token is the first in the order: ties go to the lowest index, a row of -inf
+ *   gives token 0, among NaNs the largest key wins.  kept = 1.
+ *   Sampled rows: with m = max s the mass of token j is w_j = exp((s_j - m) / T).  K1 = the first min(top_k, vocab) tokens
+ *   of the order (top_k <= 0: all).  K2 = the shortest prefix of K1 whose mass is >= top_p * mass(K1) (top_p >= 1: K2 = K1;
+ *   top_p <= 0 or NaN: the first token only).  kept = |K2|.  This is the order of transformers' warpers: temperature, then
+ *   top-k, then top-p.  The reference's demo sampler filters top-p before top-k; the two differ only when both filters
+ *   are active.
+ *   Draw (Gumbel-max): token = argmax over j in K2 of z_j = (s_j - m) / T - log(-log(u_j)), ties to the earlier token of
+ *   the order.  u_j = ((word >> 9) + 0.5) * 2^-23 (exact in fp32, never 0 or 1), word = output j & 3 of Philox4x32-10 with
+ *   key (seed low, seed high) and counter (j >> 2, pos_i, 0x51554553, 0); multipliers 0xD2511F53 / 0xCD9E8D57, key bumps
+ *   0x9E3779B9 / 0xBB67AE85 (Random123's philox4x32).
+ *   Invariance: the draw depends on (seed, pos_i, j) only -- a sequence samples the same token alone, at any row of any
+ *   batch, eagerly or from a replayed graph, bit for bit.  The top-k / top-p boundary is deterministic too: counts are
+ *   integers, and a token's mass enters as the integer floor(expf((s_j - m) / T) * 2^40), a function of its key alone, so
+ *   sums do not depend on their order.  Against the exact real-number boundary that is a relative error around 1e-6 of
+ *   mass(K1); rows whose cut lies closer to top_p * mass(K1) than that may keep one token more or fewer than float64 says.
+ *
+ * ARGUMENTS.  logits: n_rows rows of `vocab` elements, logits_stride elements apart (>= vocab; rows need 2-byte alignment
+ * only).  temperature / top_k / top_p / seed: device arrays of n_rows.  Exactly one of states (n_rows consecutive step
+ * states) / positions (int32[n_rows]) is non-NULL.  tokens (int32[n_rows]) is written for every row and always lies in
+ * [0, vocab); kept (int32[n_rows], may be NULL) receives |K2| (0 for a finished row).
+ * Stop handling: finished (int32[n_rows], in/out, may be NULL), eos_ids (device int32[n_eos], n_eos <= 8), pad_id.  A row
+ * whose flag is set emits pad_id, draws nothing and changes neither its flag nor its history; a row that samples an eos id
+ * emits it and sets its flag.
+ * History (optional, both or neither): history int32[n_rows][history_stride], history_len int32[n_rows] in/out -- the token
+ * of an unfinished row is stored at history_len[i] when that is < history_stride and the length incremented; nothing is
+ * written past a row.
+ * Closing the loop (optional, both or neither): embed [vocab][hidden] and next_input [n_rows][hidden] in the stored type --
+ * the row's workgroup copies embed[token] to next_input[i], so the launch feeds the next step's input.
+ *
+ * REFUSALS, before anything is launched and with every output untouched.  QUEST_EINVAL: a NULL required pointer, both or
+ * neither of states / positions, vocab or n_rows 0, logits_stride < vocab, an odd logits address, pad_id or an eos id outside
+ * [0, vocab), n_eos > 8, one of a pair (history / history_len, embed / next_input) without the other, an unknown dtype.
+ * QUEST_EUNSUPPORTED: vocab > 2^18.  The eos ids are device memory: outside a stream capture the entry reads them back (one
+ * wait on `stream`); while `stream` is capturing they cannot be read, and an id outside the vocabulary then simply matches
+ * no token.
+ * Not part of this entry: repetition penalty (it reorders the row, so the 16-bit key order no longer decides), min-p and
+ * typical sampling, beam search, log-prob outputs, logits processors, tokenizers.
+ */
+int quest_sample_tokens(const void* logits, uint32_t logits_stride, uint32_t vocab, uint32_t n_rows, uint32_t dtype,
+                        const float* temperature, const int32_t* top_k, const float* top_p, const uint64_t* seed,
+                        const quest_step_state_t* states, const int32_t* positions, int32_t* tokens, int32_t* kept,
+                        const int32_t* eos_ids, uint32_t n_eos, int32_t pad_id, int32_t* finished, int32_t* history,
+                        uint32_t history_stride, int32_t* history_len, const void* embed, uint32_t hidden, void* next_input,
+                        quest_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -809,6 +809,57 @@ def prefill_with_paged_kv_cache(q, kv_data, kv_indices, kv_last_page_len: int, c
 
 # ---------------------------------------------------------------- handler class
 
+SAMPLE_MAX_VOCAB = 1 << 18  # quest_sample_tokens: QUEST_EUNSUPPORTED beyond
+SAMPLE_MAX_EOS = 8
+
+
+def sample_tokens(logits, temperature, top_k, top_p, seed, tokens, *, states=None, positions=None, kept=None,
+                  eos_ids=None, pad_id: int = 0, finished=None, history=None, history_len=None, embed=None,
+                  next_input=None) -> None:
+    """One token per row of ``logits`` ``[n, vocab]`` (fp16 / bf16, contiguous rows ``logits.stride(0)`` apart, any
+    2-byte alignment) under the sampling contract of include/quest_hip.h ("Token sampling"; EXTENSION): temperature, then
+    top-k, then top-p, a Gumbel-max draw from Philox4x32-10 of (seed, position, token index); greedy for temperature 0.
+    ``temperature`` / ``top_p`` fp32 ``[n]``, ``top_k`` int32 ``[n]``, ``seed`` int64 ``[n]`` (the uint64's bits), ``tokens``
+    int32 ``[n]`` (written); exactly one of ``states`` (``[n, 8]`` int32 step states: position = ``seq_len``) /
+    ``positions`` (int32 ``[n]``).  Optional: ``kept`` int32 ``[n]``; ``finished`` int32 ``[n]`` in/out with ``eos_ids``
+    (int32, at most 8) and ``pad_id``; ``history`` int32 ``[n, stride]`` with ``history_len`` int32 ``[n]``; ``embed``
+    ``[vocab, hidden]`` with ``next_input`` ``[n, hidden]`` (the launch copies the chosen token's embedding row there)."""
+    _check_rows(logits, "logits")
+    n, vocab = logits.size(0), logits.size(1)
+    _check_half(logits, "sample_tokens", embed, next_input)
+    i32, f32 = torch.int32, torch.float32
+    for t, name, dt, numel in ((temperature, "temperature", f32, n), (top_k, "top_k", i32, n), (top_p, "top_p", f32, n),
+                               (seed, "seed", torch.int64, n), (tokens, "tokens", i32, n), (kept, "kept", i32, n),
+                               (positions, "positions", i32, n), (states, "states", i32, n * STEP_STATE_INTS),
+                               (finished, "finished", i32, n), (history_len, "history_len", i32, n),
+                               (eos_ids, "eos_ids", i32, None), (history, "history", i32, None)):
+        if t is None:
+            continue
+        _check_input(t, name)
+        _check_eq(t.dtype, dt, f"{name}.scalar_type()")
+        if numel is not None:
+            _check_eq(t.numel(), numel, f"{name}.numel()")
+    if history is not None:
+        _check_dim(2, history, "history")
+        _check_eq(history.size(0), n, "history.size(0), n")
+    hidden = 0
+    if embed is not None:
+        _check_input(embed, "embed")
+        _check_dim(2, embed, "embed")
+        _check_eq(embed.size(0), vocab, "embed.size(0), vocab")
+        hidden = embed.size(1)
+        if next_input is not None:
+            _check_input(next_input, "next_input")
+            _check_eq(next_input.numel(), n * hidden, "next_input.numel(), n * hidden")
+    ptr = lambda t: t.data_ptr() if t is not None else None
+    check(lib.quest_sample_tokens(
+        logits.data_ptr(), logits.stride(0), vocab, n, _DTYPES[logits.dtype], ptr(temperature), ptr(top_k), ptr(top_p),
+        ptr(seed), ptr(states), ptr(positions), ptr(tokens), ptr(kept), ptr(eos_ids),
+        eos_ids.numel() if eos_ids is not None else 0, int(pad_id), ptr(finished), ptr(history),
+        history.size(1) if history is not None else 0, ptr(history_len), ptr(embed), hidden, ptr(next_input),
+        _stream(logits)), "sample_tokens")
+
+
 class BatchDecodeWithPagedKVCachePyTorchWrapper:
     """bsk_ops.h:88-117 / approx_attn.cu:27-150: begin_forward plans, forward launches."""
 

@@ -112,6 +112,8 @@ SIGNATURES = {
                                                              c_vp, Batch, c_vp, c_u32, c_vp, c_vp]),
     "quest_rms_norm_forward": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_f32, c_vp]),
     "quest_prefill_with_paged_kv_cache": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, PagedKV, c_u32, ctypes.c_int, c_vp]),
+    "quest_sample_tokens": (ctypes.c_int, [c_vp, c_u32, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            c_vp, c_u32, c_i32, c_vp, c_vp, c_u32, c_vp, c_vp, c_u32, c_vp, c_vp]),
 }
 # the decode-layer projections' typed entries: <name>_dtype = <name> with `uint32_t dtype` in front of `stream`
 for _name in ("norm_gemv", "gemv_residual", "mlp_gate_up", "qkv_rope", "qkv"):

@@ -425,7 +425,7 @@ class LlamaForCausalLM(nn.Module):
         return self.lm_head(h[:, -1:, :])  # decode only needs the last position
 
     # ------------------------------------------------------------------ one hipGraph per generated token
-    def capture_decode_graph(self, fused_layers: Optional[bool] = None) -> None:
+    def capture_decode_graph(self, fused_layers: Optional[bool] = None, sampler=None) -> None:
         """Capture ONE decode step (all layers + lm_head) and keep it for ``decode_graph_step``.  ``fused_layers``
         (None, the default: on for fp16 models unless ``QUEST_FUSED_LAYER=0``, OFF for bf16 models; True / False: as
         asked, for both types): the decoder layers' projections, norms, RoPE,
@@ -438,12 +438,16 @@ class LlamaForCausalLM(nn.Module):
         the prompt has been processed (any length: while the cache holds fewer pages than the budget the
         sparse layers attend all of them, like the reference's full-attention branch).  The
         graph reads its input from ``self.graph_input`` ``[1, 1, hidden]`` and leaves the logits in
-        ``self.graph_logits``; sequence lengths live on the device (EXTENSION)."""
+        ``self.graph_logits``; sequence lengths live on the device (EXTENSION).
+        ``sampler`` (a ``quest_amd.utils.Sampler`` for one sequence; None, the default: today's graph, launch for launch):
+        the captured step ends with the sampling launch (csrc/sampling.hip), which picks the token from the logits at
+        position ``seq_len`` of the device state and writes its embedding row into ``self.graph_input`` -- a replay then
+        feeds the next one, with no host round trip in between (``generate``)."""
         ctl = self.model.iController
         ctl.set_page_budget(self.model._quest_page_budget)
-        self._capture_decode_graph(ctl, fused_layers)
+        self._capture_decode_graph(ctl, fused_layers, sampler)
 
-    def _capture_decode_graph(self, ctl, fused_layers: Optional[bool]) -> None:
+    def _capture_decode_graph(self, ctl, fused_layers: Optional[bool], sampler=None) -> None:
         """Capture one decode step of every sequence of ``ctl`` (an ``InferenceController`` is the batch of one)."""
         m, n = self.model, ctl.n_seqs
         dev = next(self.parameters()).device
@@ -465,13 +469,27 @@ class LlamaForCausalLM(nn.Module):
             logits = torch.empty(n, 1, self.config.vocab_size, dtype=dtype, device=dev)
             norm_gemv = _fused_layer_launches(ctl)[4]
 
-            def step():
+            def forward():
                 hs = m.forward_decode_fused(self.graph_input, self._graph_scores, ctl, ws)
                 norm_gemv(hs, m.norm.weight, m.norm.variance_epsilon, self.lm_head.weight, logits)
                 return logits
         else:
-            def step():
+            def forward():
                 return self.lm_head(m.forward_decode(self.graph_input, self._graph_scores, ctl))
+
+        if sampler is None:
+            step = forward
+        else:
+            if sampler.n != n or sampler.vocab_size != self.config.vocab_size:
+                raise ValueError(f"the sampler serves {sampler.n} sequences of vocabulary {sampler.vocab_size}, the step "
+                                 f"{n} of {self.config.vocab_size}")
+
+            def step():
+                out = forward()
+                # (the state was advanced at the head of the step: seq_len = the index the sampled token will occupy)
+                sampler.sample(out.view(n, -1), states=ctl.step_states, embed=m.embed_tokens.weight,
+                               next_input=self.graph_input.view(n, -1))
+                return out
 
         # Warm-up (allocator, rocBLAS workspaces) runs a real step on a dummy input: it advances the device
         # state and folds the dummy key into every sequence's current (max, min) metadata entry.  K/V bytes it wrote
@@ -481,6 +499,7 @@ class LlamaForCausalLM(nn.Module):
         pool = seqs[0].metadata_cache.pool  # (one pool for all sequences of a batch)
         pages = torch.tensor([c.metadata_cache.indicies[-1] for c in seqs], device=dev)
         saved = pool.buf[:, pages].clone()
+        saved_sampler = sampler.snapshot() if sampler is not None else None  # (the warm-up samples from the dummy step)
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), torch.inference_mode():
@@ -488,11 +507,14 @@ class LlamaForCausalLM(nn.Module):
         torch.cuda.current_stream().wait_stream(side)
         torch.cuda.synchronize()
         pool.buf[:, pages] = saved
+        if sampler is not None:
+            sampler.restore(saved_sampler)
         ctl.sync_device_state()
         self._graph = torch.cuda.CUDAGraph()
         with torch.inference_mode(), torch.cuda.graph(self._graph):
             self.graph_logits = step()
         self._graph_epoch = ctl.state_epoch
+        self._graph_sampler = sampler
 
     def decode_graph_step(self, inputs_embeds: Optional[torch.Tensor] = None,
                           input_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -535,12 +557,12 @@ class LlamaForCausalLM(nn.Module):
         finally:
             m.iController = None
 
-    def capture_decode_graph_batched(self, fused_layers: Optional[bool] = None) -> None:
+    def capture_decode_graph_batched(self, fused_layers: Optional[bool] = None, sampler=None) -> None:
         """Batched ``capture_decode_graph``: input ``self.graph_input`` ``[n, 1, hidden]``, logits
         ``self.graph_logits`` ``[n, 1, vocab]``.  ``fused_layers`` as in ``capture_decode_graph`` (default on for fp16
         models and n <= 16 unless ``QUEST_FUSED_LAYER=0``, off for bf16 models, which take them with ``fused_layers=True``):
-        4 fused launches per layer for the whole batch."""
-        self._capture_decode_graph(self.model.bController, fused_layers)
+        4 fused launches per layer for the whole batch.  ``sampler`` (for ``n`` sequences) as in ``capture_decode_graph``."""
+        self._capture_decode_graph(self.model.bController, fused_layers, sampler)
 
     def decode_graph_step_batched(self, input_ids: torch.Tensor) -> torch.Tensor:
         """One token for every sequence: ``input_ids`` ``[n]`` -> logits ``[n, 1, vocab]`` (the graph's buffer)."""
@@ -550,3 +572,64 @@ class LlamaForCausalLM(nn.Module):
         self._graph.replay()
         self.model.bController.prepare_metadata(1)
         return self.graph_logits
+
+    # ------------------------------------------------------------------ generation with device-side sampling (EXTENSION)
+    def _generate(self, ctl, capture, logits: torch.Tensor, prompt_lens, max_new_tokens: int, sampling, eos_token_id,
+                  sync_every: int, fused_layers: Optional[bool]):
+        """The loop behind ``generate`` / ``generate_batched``: ``logits`` ``[n, vocab]`` of the prompts' last positions."""
+        from ..utils.sampling import Sampler, SamplingParams
+
+        n, dev = logits.size(0), logits.device
+        if max_new_tokens < 1:
+            raise ValueError("max_new_tokens must be at least 1")
+        sampler = Sampler(n, self.config.vocab_size, dev, max_tokens=max_new_tokens, eos_token_id=eos_token_id)
+        if sampling is None or isinstance(sampling, SamplingParams):
+            sampling = [sampling or SamplingParams()] * n
+        if len(sampling) != n:
+            raise ValueError(f"{len(sampling)} sampling parameter sets for {n} sequences")
+        for i, params in enumerate(sampling):
+            sampler.set_params(i, params)
+        # the first token: an eager call of the same entry on the prefill logits (it will sit at index prompt length)
+        first = torch.empty(n, 1, self.config.hidden_size, dtype=self.lm_head.weight.dtype, device=dev)
+        sampler.sample(logits, positions=torch.tensor(list(prompt_lens), dtype=torch.int32, device=dev),
+                       embed=self.model.embed_tokens.weight, next_input=first.view(n, -1))
+        if max_new_tokens > 1 and not (sampler.eos_ids is not None and sampler.all_finished()):
+            capture(fused_layers=fused_layers, sampler=sampler)
+            with torch.inference_mode():
+                self.graph_input.copy_(first)
+            for t in range(1, max_new_tokens):
+                self._graph.replay()       # the step and its token choice; nothing is copied to the host
+                ctl.prepare_metadata(1)    # host mirror of the device-side reservation
+                if sampler.eos_ids is not None and sync_every > 0 and t % sync_every == 0 and sampler.all_finished():
+                    break
+        self.last_sampler = sampler
+        return sampler.sequences()
+
+    def generate(self, input_ids: torch.Tensor, max_new_tokens: int, sampling=None, eos_token_id=None, sync_every: int = 16,
+                 fused_layers: Optional[bool] = None) -> torch.Tensor:
+        """Generate up to ``max_new_tokens`` tokens after the prompt ``input_ids`` ``[1, L]`` (after ``quest_init``, on an
+        empty cache: ``quest_clear()`` between requests) and return them (int64, CPU), ending with the eos id when one was
+        reached.  ``sampling``: a ``quest_amd.utils.SamplingParams`` (None: greedy); ``eos_token_id``: an id or up to 8.
+        The prompt runs through the ordinary forward; the first token is an eager call of the sampling launch on its logits;
+        the rest are replays of ONE captured step that ends with the sampling launch and feeds itself (``sampler`` of
+        ``capture_decode_graph``) -- no device-to-host copy between replays; the finished flag is read every ``sync_every``
+        steps to stop early.  ``fused_layers`` as in ``capture_decode_graph``."""
+        with torch.inference_mode():
+            logits = self(input_ids=input_ids)
+        return self._generate(self.model.iController, self.capture_decode_graph, logits.view(1, -1), [input_ids.size(1)],
+                              max_new_tokens, sampling, eos_token_id, sync_every, fused_layers)[0]
+
+    def generate_batched(self, prompts, max_new_tokens: int, sampling=None, eos_token_id=None, sync_every: int = 16,
+                         fused_layers: Optional[bool] = None):
+        """``generate`` for the sequences of ``quest_init_batched``: ``prompts`` = one ``[1, L_i]`` tensor per sequence,
+        ``sampling`` one ``SamplingParams`` for all or a list of one per sequence.  Prompts are prefilled one by one
+        (``prefill_sequence``), the decode steps run all sequences per replay.  A finished sequence keeps stepping with the
+        pad id until all are finished (seen at the next flag check) or ``max_new_tokens`` is reached; the returned list
+        holds each sequence's tokens, ending with its eos id when it reached one."""
+        ctl = self.model.bController
+        if len(prompts) != ctl.n_seqs:
+            raise ValueError(f"{len(prompts)} prompts for {ctl.n_seqs} sequences")
+        with torch.inference_mode():
+            logits = torch.cat([self.prefill_sequence(i, p).view(1, -1) for i, p in enumerate(prompts)])
+        return self._generate(ctl, self.capture_decode_graph_batched, logits, [p.size(1) for p in prompts], max_new_tokens,
+                              sampling, eos_token_id, sync_every, fused_layers)

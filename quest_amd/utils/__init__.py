@@ -14,6 +14,7 @@ from .. import _kernels
 from .controller import BatchedInferenceController, InferenceController
 from .decode_wrapper import BatchDecodeWithPagedKVCacheWrapper
 from .kv_cache import KvCache
+from .sampling import Sampler, SamplingParams
 from .utils import TensorLayout
 
 __all__ = [
@@ -50,6 +51,9 @@ __all__ = [
     "decode_estimate_batched",
     "decode_topk_batched",
     "decode_sparse_attn_batched",
+    # device-side token sampling (csrc/sampling.hip)
+    "Sampler",
+    "SamplingParams",
 ]
 
 

@@ -22,8 +22,8 @@
  *     bf16 differences: metadata max / min treat patterns above 0x7f80 as NaN, a new page's entry starts from -/+ the
  *     largest finite bf16 (0xff7f / 0x7f7f) instead of -/+65504, scores are bf16_rne of the same fp32 sum, partial
  *     attention states stay fp32.  The decode-layer projections (quest_decode_norm_gemv, _gemv_residual, _mlp_gate_up,
- *     _qkv_rope, _qkv and their _batched forms) take neither a view nor a handler either: each has a typed entry
- *     <name>_dtype with `uint32_t dtype` in front of `stream`, and the untyped symbol is that entry with QUEST_DTYPE_F16.
+ *     _qkv_rope, _qkv and their _batched forms) take neither a view nor a handler either: each is one entry with
+ *     `uint32_t dtype` in front of `stream`.
  *     fp16 only: quest_decode_layer_fused_batched, which returns QUEST_EUNSUPPORTED for bf16 views
  *     (the caller issues quest_append_estimate_batched + quest_decode_forward_fused_topk_batched).
  *   - One entry per operator.  An operator that reads lengths and last pages from device-resident step state
@@ -499,91 +499,68 @@ int quest_prefill_with_paged_kv_cache(const void* q, void* o, uint32_t n_q, uint
 /*
  * Decode-token projections of a Llama decoder layer around the attention path, fused (EXTENSION; csrc/decode_layer.hip).
  * The reference leaves them to cuBLAS + PyTorch kernels: RMSNorm (quest/ops/csrc/rms_norm.cu:82-213 via
- * quest/models/llama.py:72), q/k/v projections (QuestAttention.py:88-90) + RoPE (:99, decode_page.cuh:644-728), o_proj (QuestAttention.py:175),
- * residual adds and the SwiGLU MLP (llama.py LlamaMLP).  All vectors / matrices of the call's element type (below), row-major weights [out][in]
- * (torch.nn.Linear.weight), fp32 accumulation, batch 1.
- *   quest_decode_norm_gemv     out[out_dim] = W . rmsnorm(x; gamma, eps)      (gamma NULL: out = W . x)
- *   quest_decode_gemv_residual h[out_dim]  += W . x                           (in place on the residual stream)
- *   quest_decode_mlp_gate_up   act[intermediate] = silu(Wg . n) * (Wu . n),   n = rmsnorm(h; gamma, eps)
- *   quest_decode_qkv_rope      q, k, v = Wq . n, Wk . n, Wv . n with rotate-half RoPE on q and k at position
- *                              state->seq_len - 1 (call after quest_step_state_advance_batched), n = rmsnorm(h; gamma,
- *                              eps).  inv_freq NULL: default / linear RoPE, frequency (1 / rope_scale) *
- *                              rope_theta^(-2i / head_dim); else the frequency table and attention_factor of
- *                              quest_apply_rope_in_place_dtype (QUEST_EINVAL like there)
- * Element type: every entry below is <name>_dtype(..., uint32_t dtype, stream) -- all vectors and matrices of one call have
- * the element type `dtype` (QUEST_DTYPE_F16 / QUEST_DTYPE_BF16; anything else is QUEST_EINVAL before any launch) -- and
- * <name>(..., stream), which is <name>_dtype with QUEST_DTYPE_F16.  Both types run the same kernels compiled once per type
+ * quest/models/llama.py:72), q/k/v projections (QuestAttention.py:88-90) + RoPE (:99, decode_page.cuh:644-728), o_proj
+ * (QuestAttention.py:175), residual adds and the SwiGLU MLP (llama.py LlamaMLP).  Row-major weights [out][in]
+ * (torch.nn.Linear.weight).
+ *
+ * Operators (n = rmsnorm(x or h; gamma, eps)):
+ *   norm_gemv      out[out_dim] = W . n                                       (gamma NULL: out = W . x)
+ *   gemv_residual  h[out_dim]  += W . x                                       (in place on the residual stream)
+ *   mlp_gate_up    act[intermediate] = silu(Wg . n) * (Wu . n)
+ *   qkv_rope       q, k, v = Wq . n, Wk . n, Wv . n with rotate-half RoPE on q and k at position state->seq_len - 1
+ *                  (call after quest_step_state_advance_batched).  inv_freq NULL: default / linear RoPE, frequency
+ *                  (1 / rope_scale) * rope_theta^(-2i / head_dim); else the frequency table and attention_factor of
+ *                  quest_apply_rope_in_place_dtype (QUEST_EINVAL like there)
+ *   qkv            q = Wq . n [q_rows], k = Wk . n, v = Wv . n [kv_rows], stored unrotated, for models whose q and k pass
+ *                  a per-head norm before RoPE; quest_apply_qk_norm_rope_in_place_dtype follows
+ *
+ * Forms: one entry per operator and form.  quest_decode_<operator> is one decode token; quest_decode_<operator>_batched
+ * is n_tokens <= 16 tokens at once -- one per sequence of a batch (the reference asserts batch size 1;
+ * BatchedInferenceController): x / h `[n_tokens][in]`, outputs `[n_tokens][out]` (q / k / v
+ * `[n_tokens][heads][head_dim]`), all contiguous; `states` = n_tokens consecutive quest_step_state_t records (the batched
+ * step state), token i rotated at states[i].seq_len - 1.  The weights are read once for the whole batch (MFMA row-dots:
+ * weights = A operand, tokens = the 16 columns of B); head_dim % 16 == 0 for the rotating launch.  The two forms launch
+ * different kernels, and one token through the batched form differs from the one-token form in the last bits.
+ *
+ * Element type: `dtype` (QUEST_DTYPE_F16 / QUEST_DTYPE_BF16), in front of `stream`, is the type of every vector and matrix
+ * of the call; anything else is QUEST_EINVAL before any launch.  Both types run the same kernels compiled once per type
  * (bf16: <kernel>_b16; v_dot2c_f32_bf16 / v_mfma_f32_4x4x4_16b_bf16), with the same planner cells, grids, row orders and
- * shape limits (what fp16 refuses with QUEST_EUNSUPPORTED, bf16 refuses too), and the same numeric contract: products
- * accumulate in fp32, the RMSNorm prologue rounds x * inv_rms * gamma to the element type once (as
- * quest_rms_norm_forward_dtype), SiLU * up and the rotation are computed in fp32, the residual add is
- * round(float(h) + acc), every output is rounded once, to nearest even.
+ * shape limits (what fp16 refuses with QUEST_EUNSUPPORTED, bf16 refuses too).
+ *
+ * Numeric contract: products accumulate in fp32, the RMSNorm prologue rounds x * inv_rms * gamma to the element type
+ * once (as quest_rms_norm_forward_dtype), SiLU * up and the rotation are computed in fp32, the residual add is
+ * round(float(h) + acc), every output is rounded once, to nearest even.  qkv adds the same row-dots in the same order as
+ * qkv_rope at head_dim <= 256: a lane of the one-token kernel adds a row's products in the same order whatever the
+ * workgroup shape, and the batched form is planned with the rotating launch's LDS budget, so both take the same n-token
+ * kernel -- the one quest_decode_batched_plan(hidden, q_rows + 2 kv_rows, n_tokens, 1, ...) names -- and v is
+ * bit-identical.  (Beyond head_dim 256 the rotating launch always takes the inputs-from-L2 kernel.)
  */
 int quest_decode_norm_gemv(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
-                           uint32_t out_dim, quest_stream_t stream);
-int quest_decode_norm_gemv_dtype(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
                            uint32_t out_dim, uint32_t dtype, quest_stream_t stream);
-int quest_decode_gemv_residual(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
+int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
+                                   uint32_t out_dim, uint32_t n_tokens, uint32_t dtype, quest_stream_t stream);
+int quest_decode_gemv_residual(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim, uint32_t dtype,
                                quest_stream_t stream);
-int quest_decode_gemv_residual_dtype(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim, uint32_t dtype, quest_stream_t stream);
+int quest_decode_gemv_residual_batched(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
+                                       uint32_t n_tokens, uint32_t dtype, quest_stream_t stream);
 int quest_decode_mlp_gate_up(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up, void* act,
-                             uint32_t hidden, uint32_t intermediate, quest_stream_t stream);
-int quest_decode_mlp_gate_up_dtype(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up, void* act,
                              uint32_t hidden, uint32_t intermediate, uint32_t dtype, quest_stream_t stream);
+int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
+                                     void* act, uint32_t hidden, uint32_t intermediate, uint32_t n_tokens, uint32_t dtype,
+                                     quest_stream_t stream);
 int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
                           void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
                           uint32_t head_dim, float rope_scale, float rope_theta, const float* inv_freq,
-                          float attention_factor, const quest_step_state_t* state, quest_stream_t stream);
-int quest_decode_qkv_rope_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
-                          void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads,
-                          uint32_t head_dim, float rope_scale, float rope_theta, const float* inv_freq,
                           float attention_factor, const quest_step_state_t* state, uint32_t dtype, quest_stream_t stream);
-/*
- * The same four launches for n_tokens <= 16 decode tokens at once -- one per sequence of a batch (the reference asserts
- * batch size 1; BatchedInferenceController): x / h `[n_tokens][in]`, outputs `[n_tokens][out]` (q / k / v
- * `[n_tokens][heads][head_dim]`), all contiguous; `states` = n_tokens consecutive quest_step_state_t records (the batched
- * step state), token i rotated at states[i].seq_len - 1.  The weights are read once for the whole batch (MFMA row-dots:
- * weights = A operand, tokens = the 16 columns of B); head_dim % 16 == 0 for the q/k/v launch.
- */
-int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
-                                   uint32_t out_dim, uint32_t n_tokens, quest_stream_t stream);
-int quest_decode_norm_gemv_batched_dtype(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
-                                   uint32_t out_dim, uint32_t n_tokens, uint32_t dtype, quest_stream_t stream);
-int quest_decode_gemv_residual_batched(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
-                                       uint32_t n_tokens, quest_stream_t stream);
-int quest_decode_gemv_residual_batched_dtype(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
-                                       uint32_t n_tokens, uint32_t dtype, quest_stream_t stream);
-int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
-                                     void* act, uint32_t hidden, uint32_t intermediate, uint32_t n_tokens,
-                                     quest_stream_t stream);
-int quest_decode_mlp_gate_up_batched_dtype(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
-                                     void* act, uint32_t hidden, uint32_t intermediate, uint32_t n_tokens, uint32_t dtype, quest_stream_t stream);
 int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                   const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
                                   uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
                                   const float* inv_freq, float attention_factor, const quest_step_state_t* states,
-                                  uint32_t n_tokens, quest_stream_t stream);
-int quest_decode_qkv_rope_batched_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
-                                  const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
-                                  uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
-                                  const float* inv_freq, float attention_factor, const quest_step_state_t* states,
                                   uint32_t n_tokens, uint32_t dtype, quest_stream_t stream);
-
-/* The q-k-v launch without the rotation, for models whose q and k pass a per-head norm before RoPE: RMSNorm(h) ->
- * q = Wq x [q_rows], k = Wk x, v = Wv x [kv_rows], stored unrotated; quest_apply_qk_norm_rope_in_place_dtype follows.
- * The same row-dots in the same order as quest_decode_qkv_rope / _batched at head_dim <= 256: a lane of the batch-1 kernel adds a
- * row's products in the same order whatever the workgroup shape, and the batched form (n_tokens <= 16) is planned with the
- * rotating launch's LDS budget, so both take the same n-token kernel -- the one
- * quest_decode_batched_plan(hidden, q_rows + 2 kv_rows, n_tokens, 1, ...) names -- and v is bit-identical.  (Beyond
- * head_dim 256 the rotating launch always takes the inputs-from-L2 kernel.) */
 int quest_decode_qkv(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
-                     void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows, quest_stream_t stream);
-int quest_decode_qkv_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
-                     void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows, uint32_t dtype, quest_stream_t stream);
+                     void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows, uint32_t dtype,
+                     quest_stream_t stream);
 int quest_decode_qkv_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
-                             void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows,
-                             uint32_t n_tokens, quest_stream_t stream);
-int quest_decode_qkv_batched_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
                              void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows,
                              uint32_t n_tokens, uint32_t dtype, quest_stream_t stream);
 

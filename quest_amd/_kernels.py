@@ -362,43 +362,67 @@ def _check_weight(w, out_dim: int, in_dim: int, name: str, like) -> None:
     _check_half(like, name, w)
 
 
-def decode_norm_gemv(x, gamma, eps: float, w, out) -> None:
-    """``out = w @ rmsnorm(x; gamma, eps)`` (``gamma`` None: ``out = w @ x``); x ``[in]``, w ``[out, in]``, out ``[out]``."""
+# One private body per operator: validation and the call.  ``n`` None: the one-token entry (vectors); else the n-token
+# entry (``[n, dim]`` matrices), after ``_check_tokens``.  The twelve public names below are thin calls of the five bodies.
+MAX_BATCHED_TOKENS = 16
+
+
+def _check_tokens(n: int) -> None:
+    if not 1 <= n <= MAX_BATCHED_TOKENS:
+        raise RuntimeError(f"batched decode-layer launches take 1..{MAX_BATCHED_TOKENS} tokens, got {n}")
+
+
+def _check_act(x, n, dim: int, name: str, like) -> None:
+    """An activation of the one-token (``n`` None: ``[dim]``) or the n-token (``[n, dim]``) entry."""
+    if n is None:
+        _check_vec(x, dim, name, like)
+    else:
+        _check_mat(x, n, dim, name, like)
+
+
+def _entry(name: str, n):
+    """(C entry, tail of its argument list before dtype, name for error messages) of operator ``name``'s form for ``n``."""
+    if n is None:
+        return getattr(lib, f"quest_decode_{name}"), (), f"decode_{name}"
+    return getattr(lib, f"quest_decode_{name}_batched"), (n,), f"decode_{name}_batched"
+
+
+def _norm_gemv(x, gamma, eps, w, out, n) -> None:
     out_dim, in_dim = w.shape
-    _check_vec(x, in_dim, "x", x)
-    _check_vec(out, out_dim, "out", x)
+    _check_act(x, n, in_dim, "x", x)
+    _check_act(out, n, out_dim, "out", x)
     _check_weight(w, out_dim, in_dim, "w", x)
     if gamma is not None:
         _check_vec(gamma, in_dim, "gamma", x)
-    check(lib.quest_decode_norm_gemv_dtype(x.data_ptr(), gamma.data_ptr() if gamma is not None else None, float(eps),
-                                     w.data_ptr(), out.data_ptr(), in_dim, out_dim, _DTYPES[x.dtype], _stream(x)), "decode_norm_gemv")
+    fn, tokens, what = _entry("norm_gemv", n)
+    check(fn(x.data_ptr(), gamma.data_ptr() if gamma is not None else None, float(eps), w.data_ptr(), out.data_ptr(), in_dim,
+             out_dim, *tokens, _DTYPES[x.dtype], _stream(x)), what)
 
 
-def decode_gemv_residual(x, w, h) -> None:
-    """``h += w @ x`` in place; x ``[in]``, w ``[out, in]``, h ``[out]``."""
+def _gemv_residual(x, w, h, n) -> None:
     out_dim, in_dim = w.shape
-    _check_vec(x, in_dim, "x", x)
-    _check_vec(h, out_dim, "h", x)
+    _check_act(x, n, in_dim, "x", x)
+    _check_act(h, n, out_dim, "h", x)
     _check_weight(w, out_dim, in_dim, "w", x)
-    check(lib.quest_decode_gemv_residual_dtype(x.data_ptr(), w.data_ptr(), h.data_ptr(), in_dim, out_dim, _DTYPES[x.dtype], _stream(x)),
-          "decode_gemv_residual")
+    fn, tokens, what = _entry("gemv_residual", n)
+    check(fn(x.data_ptr(), w.data_ptr(), h.data_ptr(), in_dim, out_dim, *tokens, _DTYPES[x.dtype], _stream(x)), what)
 
 
-def decode_mlp_gate_up(h, gamma, eps: float, w_gate, w_up, act) -> None:
-    """``act = silu(w_gate @ n) * (w_up @ n)`` with ``n = rmsnorm(h; gamma, eps)``."""
+def _mlp_gate_up(h, gamma, eps, w_gate, w_up, act, n) -> None:
     inter, hidden = w_gate.shape
-    _check_vec(h, hidden, "h", h)
+    _check_act(h, n, hidden, "h", h)
     _check_vec(gamma, hidden, "gamma", h)
-    _check_vec(act, inter, "act", h)
+    _check_act(act, n, inter, "act", h)
     _check_weight(w_gate, inter, hidden, "w_gate", h)
     _check_weight(w_up, inter, hidden, "w_up", h)
-    check(lib.quest_decode_mlp_gate_up_dtype(h.data_ptr(), gamma.data_ptr(), float(eps), w_gate.data_ptr(), w_up.data_ptr(),
-                                       act.data_ptr(), hidden, inter, _DTYPES[h.dtype], _stream(h)), "decode_mlp_gate_up")
+    fn, tokens, what = _entry("mlp_gate_up", n)
+    check(fn(h.data_ptr(), gamma.data_ptr(), float(eps), w_gate.data_ptr(), w_up.data_ptr(), act.data_ptr(), hidden, inter,
+             *tokens, _DTYPES[h.dtype], _stream(h)), what)
 
 
-def _qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n: int):
-    """Validation and leading C arguments shared by every q/k/v projection launch (``decode_qkv*``, ``decode_qkv_rope*``);
-    ``n`` tokens."""
+def _qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n):
+    """Validation and leading C arguments shared by the two q/k/v projection operators; ``n`` tokens (None: one)."""
+    n = 1 if n is None else n
     hidden = wq.size(1)
     _check_mat(h, n, hidden, "h", h)
     _check_vec(gamma, hidden, "gamma", h)
@@ -412,121 +436,103 @@ def _qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n: int):
             k.data_ptr(), v.data_ptr(), hidden)
 
 
-def _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim: int, state, n: int):
-    """``_qkv_args`` plus what the four rotating ``decode_qkv_rope*`` launches add: ``state`` = the tokens' step state(s)
-    ``[n, 8]`` int32, heads counted in ``head_dim``."""
+def _qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, head_dim: int, rope_scale, rope_theta, inv_freq, attention_factor, state,
+              n) -> None:
+    """The rotating q/k/v launch: ``state`` = the tokens' step state(s) ``[n, 8]`` int32, heads counted in ``head_dim``;
+    ``inv_freq`` None: the closed form (``rope_scale``, ``rope_theta``), else the frequency table (the ``_freqs`` names)."""
     args = _qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n)
     _check_input(state, "state")
-    _check_eq(state.numel(), n * STEP_STATE_INTS, "states.numel(), n * 8")
+    _check_eq(state.numel(), (1 if n is None else n) * STEP_STATE_INTS, "states.numel(), n * 8")
     _check_eq(wq.size(0) % head_dim, 0, "wq.size(0) % head_dim, 0")
-    return args + (wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim))
+    fn, tokens, what = _entry("qkv_rope", n)
+    if inv_freq is not None:
+        _check_rope_table(inv_freq, head_dim)
+        what += "_freqs"
+    check(fn(*args, wq.size(0) // head_dim, wk.size(0) // head_dim, int(head_dim), float(rope_scale), float(rope_theta),
+             inv_freq.data_ptr() if inv_freq is not None else None, float(attention_factor), state.data_ptr(), *tokens,
+             _DTYPES[h.dtype], _stream(h)), what)
+
+
+def _qkv(h, gamma, eps, wq, wk, wv, q, k, v, n) -> None:
+    fn, tokens, what = _entry("qkv", n)
+    check(fn(*_qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n), wq.size(0), wk.size(0), *tokens, _DTYPES[h.dtype], _stream(h)),
+          what)
+
+
+def decode_norm_gemv(x, gamma, eps: float, w, out) -> None:
+    """``out = w @ rmsnorm(x; gamma, eps)`` (``gamma`` None: ``out = w @ x``); x ``[in]``, w ``[out, in]``, out ``[out]``."""
+    _norm_gemv(x, gamma, eps, w, out, None)
+
+
+def decode_gemv_residual(x, w, h) -> None:
+    """``h += w @ x`` in place; x ``[in]``, w ``[out, in]``, h ``[out]``."""
+    _gemv_residual(x, w, h, None)
+
+
+def decode_mlp_gate_up(h, gamma, eps: float, w_gate, w_up, act) -> None:
+    """``act = silu(w_gate @ n) * (w_up @ n)`` with ``n = rmsnorm(h; gamma, eps)``."""
+    _mlp_gate_up(h, gamma, eps, w_gate, w_up, act, None)
 
 
 def decode_qkv_rope(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, rope_scale: float, rope_theta: float,
                     state) -> None:
     """q ``[1, Hq, D]``, k / v ``[1, Hkv, D]`` = projections of ``rmsnorm(h; gamma, eps)`` with RoPE on q and k at the
     position ``state.seq_len - 1`` (the device-resident step state, after ``step_state_advance_batched``)."""
-    args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, state, 1)
-    check(lib.quest_decode_qkv_rope_dtype(*args, float(rope_scale), float(rope_theta), None, 1.0, state.data_ptr(), _DTYPES[h.dtype], _stream(h)),
-          "decode_qkv_rope")
+    _qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, rope_scale, rope_theta, None, 1.0, state, None)
 
 
 def decode_qkv_rope_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, inv_freq, attention_factor: float,
                           state) -> None:
     """``decode_qkv_rope`` with the RoPE frequency table of ``apply_rope_in_place_freqs`` (llama3 / yarn)."""
-    args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, state, 1)
-    _check_rope_table(inv_freq, head_dim)
-    check(lib.quest_decode_qkv_rope_dtype(*args, 1.0, 1.0, inv_freq.data_ptr(), float(attention_factor), state.data_ptr(),
-                                    _DTYPES[h.dtype], _stream(h)), "decode_qkv_rope_freqs")
+    _qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, 1.0, 1.0, inv_freq, attention_factor, state, None)
 
 
 def decode_qkv(h, gamma, eps: float, wq, wk, wv, q, k, v) -> None:
     """q ``[1, Hq, D]``, k / v ``[1, Hkv, D]`` = projections of ``rmsnorm(h; gamma, eps)``, NOT rotated: the q-k-v launch of
     models with a per-head q/k norm, which ``apply_qk_norm_rope_in_place`` follows."""
-    check(lib.quest_decode_qkv_dtype(*_qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, 1), wq.size(0), wk.size(0), _DTYPES[h.dtype], _stream(h)),
-          "decode_qkv")
+    _qkv(h, gamma, eps, wq, wk, wv, q, k, v, None)
 
 
-# ---- the fused decode-layer launches for n <= 16 tokens (one per sequence of a batch)
+# ---- the same for n <= 16 tokens (one per sequence of a batch)
 
-MAX_BATCHED_TOKENS = 16
-
-
-def _check_tokens(n: int) -> None:
-    if not 1 <= n <= MAX_BATCHED_TOKENS:
-        raise RuntimeError(f"batched decode-layer launches take 1..{MAX_BATCHED_TOKENS} tokens, got {n}")
+def _tokens(x, in_dim: int) -> int:
+    n = x.numel() // in_dim
+    _check_tokens(n)
+    return n
 
 
 def decode_norm_gemv_batched(x, gamma, eps: float, w, out) -> None:
     """``out[i] = w @ rmsnorm(x[i]; gamma, eps)`` (``gamma`` None: no norm); x ``[n, in]``, out ``[n, out]``."""
-    out_dim, in_dim = w.shape
-    n = x.numel() // in_dim
-    _check_tokens(n)
-    _check_mat(x, n, in_dim, "x", x)
-    _check_mat(out, n, out_dim, "out", x)
-    _check_weight(w, out_dim, in_dim, "w", x)
-    if gamma is not None:
-        _check_vec(gamma, in_dim, "gamma", x)
-    check(lib.quest_decode_norm_gemv_batched_dtype(x.data_ptr(), gamma.data_ptr() if gamma is not None else None, float(eps),
-                                             w.data_ptr(), out.data_ptr(), in_dim, out_dim, n, _DTYPES[x.dtype], _stream(x)),
-          "decode_norm_gemv_batched")
+    _norm_gemv(x, gamma, eps, w, out, _tokens(x, w.size(1)))
 
 
 def decode_gemv_residual_batched(x, w, h) -> None:
     """``h[i] += w @ x[i]`` in place; x ``[n, in]``, h ``[n, out]``."""
-    out_dim, in_dim = w.shape
-    n = x.numel() // in_dim
-    _check_tokens(n)
-    _check_mat(x, n, in_dim, "x", x)
-    _check_mat(h, n, out_dim, "h", x)
-    _check_weight(w, out_dim, in_dim, "w", x)
-    check(lib.quest_decode_gemv_residual_batched_dtype(x.data_ptr(), w.data_ptr(), h.data_ptr(), in_dim, out_dim, n, _DTYPES[x.dtype], _stream(x)),
-          "decode_gemv_residual_batched")
+    _gemv_residual(x, w, h, _tokens(x, w.size(1)))
 
 
 def decode_mlp_gate_up_batched(h, gamma, eps: float, w_gate, w_up, act) -> None:
     """``act[i] = silu(w_gate @ n_i) * (w_up @ n_i)``, ``n_i = rmsnorm(h[i]; gamma, eps)``; h ``[n, hidden]``."""
-    inter, hidden = w_gate.shape
-    n = h.numel() // hidden
-    _check_tokens(n)
-    _check_mat(h, n, hidden, "h", h)
-    _check_vec(gamma, hidden, "gamma", h)
-    _check_mat(act, n, inter, "act", h)
-    _check_weight(w_gate, inter, hidden, "w_gate", h)
-    _check_weight(w_up, inter, hidden, "w_up", h)
-    check(lib.quest_decode_mlp_gate_up_batched_dtype(h.data_ptr(), gamma.data_ptr(), float(eps), w_gate.data_ptr(),
-                                               w_up.data_ptr(), act.data_ptr(), hidden, inter, n, _DTYPES[h.dtype], _stream(h)),
-          "decode_mlp_gate_up_batched")
+    _mlp_gate_up(h, gamma, eps, w_gate, w_up, act, _tokens(h, w_gate.size(1)))
 
 
 def decode_qkv_rope_batched(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, rope_scale: float,
                             rope_theta: float, states) -> None:
     """q ``[n, Hq, D]``, k / v ``[n, Hkv, D]`` = projections of ``rmsnorm(h[i]; gamma, eps)``, RoPE on q and k at
     ``states[i].seq_len - 1`` (``states``: the batched step state ``[n, 8]`` int32)."""
-    n = h.numel() // wq.size(1)
-    _check_tokens(n)
-    args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, states, n)
-    check(lib.quest_decode_qkv_rope_batched_dtype(*args, float(rope_scale), float(rope_theta), None, 1.0, states.data_ptr(), n,
-                                            _DTYPES[h.dtype], _stream(h)), "decode_qkv_rope_batched")
+    _qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, rope_scale, rope_theta, None, 1.0, states, _tokens(h, wq.size(1)))
 
 
 def decode_qkv_rope_batched_freqs(h, gamma, eps: float, wq, wk, wv, q, k, v, head_dim: int, inv_freq,
                                   attention_factor: float, states) -> None:
     """``decode_qkv_rope_batched`` with the RoPE frequency table of ``apply_rope_in_place_freqs`` (llama3 / yarn)."""
-    n = h.numel() // wq.size(1)
-    _check_tokens(n)
-    args = _qkv_rope_args(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, states, n)
-    _check_rope_table(inv_freq, head_dim)
-    check(lib.quest_decode_qkv_rope_batched_dtype(*args, 1.0, 1.0, inv_freq.data_ptr(), float(attention_factor),
-                                            states.data_ptr(), n, _DTYPES[h.dtype], _stream(h)), "decode_qkv_rope_batched_freqs")
+    _qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, head_dim, 1.0, 1.0, inv_freq, attention_factor, states,
+              _tokens(h, wq.size(1)))
 
 
 def decode_qkv_batched(h, gamma, eps: float, wq, wk, wv, q, k, v) -> None:
     """``decode_qkv`` for n <= 16 tokens: h ``[n, hidden]``, q ``[n, Hq, D]``, k / v ``[n, Hkv, D]``."""
-    n = h.numel() // wq.size(1)
-    _check_tokens(n)
-    check(lib.quest_decode_qkv_batched_dtype(*_qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, n), wq.size(0), wk.size(0), n,
-                                       _DTYPES[h.dtype], _stream(h)), "decode_qkv_batched")
+    _qkv(h, gamma, eps, wq, wk, wv, q, k, v, _tokens(h, wq.size(1)))
 
 
 # ---- state-driven (graph-replayable) forms: EXTENSIONS, see include/quest_hip.h quest_step_state_t.  One launch serves

@@ -39,7 +39,8 @@ class Batch(ctypes.Structure):
                 ("page_budgets", c_vp)]
 
 
-# name -> (restype, argtypes); must list every function include/quest_hip.h declares
+# name -> (restype, argtypes); must list every function include/quest_hip.h declares.  The decode-layer projections
+# (quest_decode_norm_gemv .. quest_decode_qkv_batched) end in (uint32_t dtype, stream).
 SIGNATURES = {
     "quest_error_string": (ctypes.c_char_p, [ctypes.c_int]),
     "quest_build_info": (ctypes.c_char_p, []),
@@ -89,21 +90,24 @@ SIGNATURES = {
     "quest_decode_set_selection_out": (ctypes.c_int, [c_vp, c_vp, c_vp]),
     "quest_decode_set_front_end": (ctypes.c_int, [c_vp, ctypes.c_int]),
     "quest_apply_rope_in_place": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_u32, c_f32, c_f32, c_vp]),
-    "quest_decode_norm_gemv": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_u32, c_vp]),
-    "quest_decode_gemv_residual": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_vp]),
-    "quest_decode_mlp_gate_up": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_u32, c_u32, c_vp]),
+    "quest_decode_norm_gemv": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
+    "quest_decode_gemv_residual": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
+    "quest_decode_mlp_gate_up": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
     "quest_decode_qkv_rope": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32,
-                                              c_u32, c_f32, c_f32, c_vp, c_f32, c_vp, c_vp]),
-    "quest_decode_norm_gemv_batched": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
-    "quest_decode_gemv_residual_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
-    "quest_decode_mlp_gate_up_batched": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
+                                              c_u32, c_f32, c_f32, c_vp, c_f32, c_vp, c_u32, c_vp]),
+    "quest_decode_norm_gemv_batched": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_vp]),
+    "quest_decode_gemv_residual_batched": (ctypes.c_int, [c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_vp]),
+    "quest_decode_mlp_gate_up_batched": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32,
+                                                         c_vp]),
     "quest_decode_qkv_rope_batched": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32,
-                                                      c_u32, c_u32, c_f32, c_f32, c_vp, c_f32, c_vp, c_u32, c_vp]),
+                                                      c_u32, c_u32, c_f32, c_f32, c_vp, c_f32, c_vp, c_u32, c_u32,
+                                                      c_vp]),
     "quest_apply_qk_norm_rope_in_place_dtype": (ctypes.c_int, [c_vp, c_vp, c_u32, c_u32, c_u32, c_u32, c_u32, c_vp, c_vp,
                                                                 c_f32, c_f32, c_f32, c_vp, c_f32, c_vp, c_u32, c_vp]),
-    "quest_decode_qkv": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_vp]),
+    "quest_decode_qkv": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32, c_u32,
+                                         c_vp]),
     "quest_decode_qkv_batched": (ctypes.c_int, [c_vp, c_vp, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_u32, c_u32, c_u32,
-                                                 c_u32, c_vp]),
+                                                 c_u32, c_u32, c_vp]),
     "quest_decode_batched_plan": (ctypes.c_int, [c_u32, c_u32, c_u32, ctypes.c_int, c_vp]),
     "quest_estimate_plan": (ctypes.c_int, [c_u32, c_u32, c_u32, c_u32, ctypes.c_int, c_vp]),
     "quest_estimate_planes_bytes": (ctypes.c_uint64, [c_u32, c_u32]),
@@ -115,11 +119,6 @@ SIGNATURES = {
     "quest_sample_tokens": (ctypes.c_int, [c_vp, c_u32, c_u32, c_u32, c_u32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             c_vp, c_u32, c_i32, c_vp, c_vp, c_u32, c_vp, c_vp, c_u32, c_vp, c_vp]),
 }
-# the decode-layer projections' typed entries: <name>_dtype = <name> with `uint32_t dtype` in front of `stream`
-for _name in ("norm_gemv", "gemv_residual", "mlp_gate_up", "qkv_rope", "qkv"):
-    for _name in (f"quest_decode_{_name}", f"quest_decode_{_name}_batched"):
-        _res, _args = SIGNATURES[_name]
-        SIGNATURES[_name + "_dtype"] = (_res, _args[:-1] + [c_u32, _args[-1]])
 
 
 def verify_build(lib_path: str, src_root: str = None) -> None:

@@ -363,22 +363,14 @@ static int launch_batched(const SkinnyArgs& a, uint32_t virtual_rows, hipStream_
 
 using namespace quest;
 
-// ---- GemvArgs of the four launches, as the single-token and the n-token entries both fill them
+// ---- The five projection operators.  Each is one host function that fills the GemvArgs, validates, and launches the
+// single-token kernel or -- batched -- the n-token one (x: [n_tokens][in_dim], outputs [n_tokens][out_dim], contiguous);
+// its two C entries are the two values of `batched`.  Order of refusals: unknown dtype, null operand / zero dimension
+// (QUEST_EINVAL); then n_tokens outside 1..16 (QUEST_EINVAL, launch_batched) and in_dim % 8 (QUEST_EUNSUPPORTED).
 static GemvArgs plain_args(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim, uint32_t out_dim) {
     GemvArgs p{};
     p.x = (const half_t*)x, p.gamma = (const half_t*)gamma, p.eps = eps, p.in_dim = in_dim;
     p.w[0] = (const half_t*)w, p.rows[0] = out_dim, p.out[0] = (half_t*)out;
-    return p;
-}
-static GemvArgs residual_args(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim) {
-    GemvArgs p = plain_args(x, nullptr, 0.f, w, h, in_dim, out_dim);
-    p.residual = (const half_t*)h;
-    return p;
-}
-static GemvArgs gate_up_args(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up, void* act,
-                             uint32_t hidden, uint32_t intermediate) {
-    GemvArgs p = plain_args(h, gamma, eps, w_gate, act, hidden, intermediate);
-    p.w[1] = (const half_t*)w_up, p.rows[1] = intermediate;
     return p;
 }
 // n-token form of a launch: contiguous rows of inputs and of the (first) output
@@ -389,33 +381,65 @@ static SkinnyArgs skinny_args(const GemvArgs& g, uint32_t n_tokens) {
     return a;
 }
 
-extern "C" int quest_decode_norm_gemv_dtype(const void* x, const void* gamma, float eps, const void* w, void* out,
-                                      uint32_t in_dim, uint32_t out_dim, uint32_t dtype, quest_stream_t stream) {
+static int norm_gemv(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim, uint32_t out_dim,
+                     bool batched, uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
     if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!x || !w || !out || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
+    const GemvArgs p = plain_args(x, gamma, eps, w, out, in_dim, out_dim);
+    const bool bf = dtype == QUEST_DTYPE_BF16;
+    if (batched) return launch_batched<kGvPlain>(skinny_args(p, n_tokens), out_dim, (hipStream_t)stream, bf);
     if (in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
-    return launch_gemv<kGvPlain>(plain_args(x, gamma, eps, w, out, in_dim, out_dim), out_dim, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
+    return launch_gemv<kGvPlain>(p, out_dim, (hipStream_t)stream, bf);
 }
 
-extern "C" int quest_decode_gemv_residual_dtype(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
-                                          uint32_t dtype, quest_stream_t stream) {
+static int gemv_residual(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim, bool batched,
+                         uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
     if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!x || !w || !h || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
+    GemvArgs p = plain_args(x, nullptr, 0.f, w, h, in_dim, out_dim);
+    p.residual = (const half_t*)h;
+    const bool bf = dtype == QUEST_DTYPE_BF16;
+    if (batched) {
+        SkinnyArgs a = skinny_args(p, n_tokens);
+#ifdef QUEST_PS_TIMELINE
+        if (const char* e = quest_tuning_env("QUEST_PS_DEBUG_PTR")) a.g.out[2] = reinterpret_cast<half_t*>(strtoull(e, nullptr, 0));
+#endif
+        return launch_batched<kGvResidual>(a, out_dim, (hipStream_t)stream, bf);
+    }
     if (in_dim % 8 != 0) return QUEST_EUNSUPPORTED;
-    return launch_gemv<kGvResidual>(residual_args(x, w, h, in_dim, out_dim), out_dim, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
+    return launch_gemv<kGvResidual>(p, out_dim, (hipStream_t)stream, bf);
 }
 
-extern "C" int quest_decode_mlp_gate_up_dtype(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
-                                        void* act, uint32_t hidden, uint32_t intermediate, uint32_t dtype, quest_stream_t stream) {
+static int mlp_gate_up(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up, void* act,
+                       uint32_t hidden, uint32_t intermediate, bool batched, uint32_t n_tokens, uint32_t dtype,
+                       quest_stream_t stream) {
     if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
     if (!h || !gamma || !w_gate || !w_up || !act || hidden == 0 || intermediate == 0) return QUEST_EINVAL;
+    GemvArgs p = plain_args(h, gamma, eps, w_gate, act, hidden, intermediate);
+    p.w[1] = (const half_t*)w_up, p.rows[1] = intermediate;
+    const bool bf = dtype == QUEST_DTYPE_BF16;
+    if (batched) return launch_batched<kGvSiluMul>(skinny_args(p, n_tokens), 2 * intermediate, (hipStream_t)stream, bf);
     if (hidden % 8 != 0) return QUEST_EUNSUPPORTED;
-    return launch_gemv<kGvSiluMul>(gate_up_args(h, gamma, eps, w_gate, w_up, act, hidden, intermediate), 2 * intermediate,
-                                   (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
+    return launch_gemv<kGvSiluMul>(p, 2 * intermediate, (hipStream_t)stream, bf);
+}
+
+// GemvArgs of a launch with the three matrices Wq, Wk, Wv
+static GemvArgs qkv_args(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
+                         void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows) {
+    GemvArgs p = plain_args(h, gamma, eps, wq, q, hidden, q_rows);
+    p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
+    p.rows[1] = p.rows[2] = kv_rows;
+    p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
+    return p;
+}
+static SkinnyArgs qkv_skinny_args(const GemvArgs& g, uint32_t n_tokens) {
+    SkinnyArgs a = skinny_args(g, n_tokens);
+    a.out_stride[1] = g.rows[1], a.out_stride[2] = g.rows[2];
+    return a;
 }
 
 // The rotating q-k-v launch: closed form (inv_freq NULL) or a frequency table, as quest_apply_rope_in_place_dtype.
-// batched: the n-token launch (one state per token), else the single-token one (`states` = the one state)
+// batched: one state per token, else `states` = the one state
 static int qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
                     void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
                     float rope_scale, float rope_theta, const float* inv_freq, float attention_factor,
@@ -427,22 +451,63 @@ static int qkv_rope(const void* h, const void* gamma, float eps, const void* wq,
     // one token: a wave's 4 row-dots = two rotation pairs of one head; n tokens: a 16-row block = 8 rotation pairs of ONE
     // head of ONE matrix
     if (batched ? head_dim % 16 != 0 : (hidden % 8 != 0 || head_dim % 4 != 0)) return QUEST_EUNSUPPORTED;
-    GemvArgs p = plain_args(h, gamma, eps, wq, q, hidden, num_qo_heads * head_dim);
-    p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
-    p.rows[1] = p.rows[2] = num_kv_heads * head_dim;
-    p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
+    GemvArgs p = qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads * head_dim, num_kv_heads * head_dim);
     p.head_dim = head_dim, p.state = states;
     p.rcp_scale = inv_freq ? 1.0f : 1.0f / rope_scale, p.log2_rcp_theta = inv_freq ? 0.f : -log2f(rope_theta);
     p.inv_freq = inv_freq, p.attn_factor = inv_freq ? attention_factor : 1.0f;
     const uint32_t rows = p.rows[0] + p.rows[1] + p.rows[2];
     if (!batched) return launch_gemv<kGvQkvRope>(p, rows, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
-    SkinnyArgs a = skinny_args(p, n_tokens);
-    a.out_stride[1] = p.rows[1], a.out_stride[2] = p.rows[2];
+    SkinnyArgs a = qkv_skinny_args(p, n_tokens);
     a.state_stride = 1;
     return launch_batched<kGvQkvRope>(a, rows, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
 }
 
-extern "C" int quest_decode_qkv_rope_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+// q, k, v projections WITHOUT the rotation (models with a per-head q/k norm between the projection and RoPE: the norm
+// needs a whole head row, which this launch spreads over several workgroups -- quest_apply_qk_norm_rope_in_place_dtype
+// follows as a launch of its own).  The plain launch with three matrices: the same row-dots in the same k order as
+// the rotating launch, the epilogue stores them as they are; batched, it is planned as the rotating launch (plan_as_rope).
+static int qkv(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q, void* k,
+               void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows, bool batched, uint32_t n_tokens, uint32_t dtype,
+               quest_stream_t stream) {
+    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
+    if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v) return QUEST_EINVAL;
+    if (hidden == 0 || q_rows == 0 || kv_rows == 0) return QUEST_EINVAL;
+    const GemvArgs p = qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows);
+    const bool bf = dtype == QUEST_DTYPE_BF16;
+    if (batched) return launch_batched<kGvPlain>(qkv_skinny_args(p, n_tokens), q_rows + 2 * kv_rows, (hipStream_t)stream, bf, true);
+    if (hidden % 8 != 0) return QUEST_EUNSUPPORTED;
+    return launch_gemv<kGvPlain>(p, q_rows + 2 * kv_rows, (hipStream_t)stream, bf);
+}
+
+// ---- the C entries: one per operator and form
+extern "C" int quest_decode_norm_gemv(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
+                                      uint32_t out_dim, uint32_t dtype, quest_stream_t stream) {
+    return norm_gemv(x, gamma, eps, w, out, in_dim, out_dim, false, 0, dtype, stream);
+}
+extern "C" int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out,
+                                              uint32_t in_dim, uint32_t out_dim, uint32_t n_tokens, uint32_t dtype,
+                                              quest_stream_t stream) {
+    return norm_gemv(x, gamma, eps, w, out, in_dim, out_dim, true, n_tokens, dtype, stream);
+}
+extern "C" int quest_decode_gemv_residual(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
+                                          uint32_t dtype, quest_stream_t stream) {
+    return gemv_residual(x, w, h, in_dim, out_dim, false, 0, dtype, stream);
+}
+extern "C" int quest_decode_gemv_residual_batched(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
+                                                  uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
+    return gemv_residual(x, w, h, in_dim, out_dim, true, n_tokens, dtype, stream);
+}
+extern "C" int quest_decode_mlp_gate_up(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
+                                        void* act, uint32_t hidden, uint32_t intermediate, uint32_t dtype,
+                                        quest_stream_t stream) {
+    return mlp_gate_up(h, gamma, eps, w_gate, w_up, act, hidden, intermediate, false, 0, dtype, stream);
+}
+extern "C" int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma, float eps, const void* w_gate,
+                                                const void* w_up, void* act, uint32_t hidden, uint32_t intermediate,
+                                                uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
+    return mlp_gate_up(h, gamma, eps, w_gate, w_up, act, hidden, intermediate, true, n_tokens, dtype, stream);
+}
+extern "C" int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                      const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads,
                                      uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta,
                                      const float* inv_freq, float attention_factor, const quest_step_state_t* state,
@@ -450,63 +515,7 @@ extern "C" int quest_decode_qkv_rope_dtype(const void* h, const void* gamma, flo
     return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta,
                     inv_freq, attention_factor, state, false, 0, dtype, stream);
 }
-
-// q, k, v projections WITHOUT the rotation (models with a per-head q/k norm between the projection and RoPE: the norm
-// needs a whole head row, which this launch spreads over several workgroups -- quest_apply_qk_norm_rope_in_place_dtype
-// follows as a launch of its own).  The plain launch with three matrices: the same row-dots in the same k order as
-// quest_decode_qkv_rope*, the epilogue stores them as they are.
-static GemvArgs qkv_args(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv, void* q,
-                         void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows) {
-    GemvArgs p = plain_args(h, gamma, eps, wq, q, hidden, q_rows);
-    p.w[1] = (const half_t*)wk, p.w[2] = (const half_t*)wv;
-    p.rows[1] = p.rows[2] = kv_rows;
-    p.out[1] = (half_t*)k, p.out[2] = (half_t*)v;
-    return p;
-}
-
-extern "C" int quest_decode_qkv_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void*
-                                      wv,
-                                void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows,
-                                uint32_t dtype, quest_stream_t stream) {
-    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
-    if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v) return QUEST_EINVAL;
-    if (hidden == 0 || q_rows == 0 || kv_rows == 0) return QUEST_EINVAL;
-    if (hidden % 8 != 0) return QUEST_EUNSUPPORTED;
-    return launch_gemv<kGvPlain>(qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows), q_rows + 2 * kv_rows,
-                                 (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
-}
-
-// ---- the same for n_tokens <= 16 decode tokens (x: [n_tokens][in_dim], outputs [n_tokens][out_dim], contiguous)
-extern "C" int quest_decode_norm_gemv_batched_dtype(const void* x, const void* gamma, float eps, const void* w, void* out,
-                                              uint32_t in_dim, uint32_t out_dim, uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
-    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
-    if (!x || !w || !out || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
-    return launch_batched<kGvPlain>(skinny_args(plain_args(x, gamma, eps, w, out, in_dim, out_dim), n_tokens), out_dim,
-                                    (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
-}
-
-extern "C" int quest_decode_gemv_residual_batched_dtype(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t
-                                                        out_dim,
-                                                  uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
-    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
-    if (!x || !w || !h || in_dim == 0 || out_dim == 0) return QUEST_EINVAL;
-    SkinnyArgs a = skinny_args(residual_args(x, w, h, in_dim, out_dim), n_tokens);
-#ifdef QUEST_PS_TIMELINE
-    if (const char* e = quest_tuning_env("QUEST_PS_DEBUG_PTR")) a.g.out[2] = reinterpret_cast<half_t*>(strtoull(e, nullptr, 0));
-#endif
-    return launch_batched<kGvResidual>(a, out_dim, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
-}
-
-extern "C" int quest_decode_mlp_gate_up_batched_dtype(const void* h, const void* gamma, float eps, const void* w_gate,
-                                                const void* w_up, void* act, uint32_t hidden, uint32_t intermediate,
-                                                uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
-    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
-    if (!h || !gamma || !w_gate || !w_up || !act || hidden == 0 || intermediate == 0) return QUEST_EINVAL;
-    SkinnyArgs a = skinny_args(gate_up_args(h, gamma, eps, w_gate, w_up, act, hidden, intermediate), n_tokens);
-    return launch_batched<kGvSiluMul>(a, 2 * intermediate, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16);
-}
-
-extern "C" int quest_decode_qkv_rope_batched_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                              const void* wv, void* q, void* k, void* v, uint32_t hidden,
                                              uint32_t num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim,
                                              float rope_scale, float rope_theta, const float* inv_freq,
@@ -515,72 +524,15 @@ extern "C" int quest_decode_qkv_rope_batched_dtype(const void* h, const void* ga
     return qkv_rope(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim, rope_scale, rope_theta,
                     inv_freq, attention_factor, states, true, n_tokens, dtype, stream);
 }
-
-extern "C" int quest_decode_qkv_batched_dtype(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
+extern "C" int quest_decode_qkv(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
+                                void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows, uint32_t dtype,
+                                quest_stream_t stream) {
+    return qkv(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows, false, 0, dtype, stream);
+}
+extern "C" int quest_decode_qkv_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
                                         const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows,
                                         uint32_t kv_rows, uint32_t n_tokens, uint32_t dtype, quest_stream_t stream) {
-    if (dtype > QUEST_DTYPE_BF16) return QUEST_EINVAL;
-    if (!h || !gamma || !wq || !wk || !wv || !q || !k || !v) return QUEST_EINVAL;
-    if (hidden == 0 || q_rows == 0 || kv_rows == 0) return QUEST_EINVAL;
-    SkinnyArgs a = skinny_args(qkv_args(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows), n_tokens);
-    a.out_stride[1] = a.out_stride[2] = kv_rows;
-    return launch_batched<kGvPlain>(a, q_rows + 2 * kv_rows, (hipStream_t)stream, dtype == QUEST_DTYPE_BF16, true);
-}
-
-// ---- the untyped symbols: fp16
-extern "C" int quest_decode_norm_gemv(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t in_dim,
-                                      uint32_t out_dim, quest_stream_t stream) {
-    return quest_decode_norm_gemv_dtype(x, gamma, eps, w, out, in_dim, out_dim, QUEST_DTYPE_F16, stream);
-}
-extern "C" int quest_decode_gemv_residual(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
-                                          quest_stream_t stream) {
-    return quest_decode_gemv_residual_dtype(x, w, h, in_dim, out_dim, QUEST_DTYPE_F16, stream);
-}
-extern "C" int quest_decode_mlp_gate_up(const void* h, const void* gamma, float eps, const void* w_gate, const void* w_up,
-                                        void* act, uint32_t hidden, uint32_t intermediate, quest_stream_t stream) {
-    return quest_decode_mlp_gate_up_dtype(h, gamma, eps, w_gate, w_up, act, hidden, intermediate, QUEST_DTYPE_F16, stream);
-}
-extern "C" int quest_decode_qkv_rope(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void*
-                                     wv, void* q, void* k, void* v, uint32_t hidden, uint32_t num_qo_heads, uint32_t
-                                     num_kv_heads, uint32_t head_dim, float rope_scale, float rope_theta, const float*
-                                     inv_freq, float attention_factor, const quest_step_state_t* state, quest_stream_t stream)
-                                     {
-    return quest_decode_qkv_rope_dtype(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads, head_dim,
-                                       rope_scale, rope_theta, inv_freq, attention_factor, state, QUEST_DTYPE_F16, stream);
-}
-extern "C" int quest_decode_qkv(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const void* wv,
-                                void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t kv_rows, quest_stream_t
-                                stream) {
-    return quest_decode_qkv_dtype(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows, QUEST_DTYPE_F16, stream);
-}
-extern "C" int quest_decode_norm_gemv_batched(const void* x, const void* gamma, float eps, const void* w, void* out, uint32_t
-                                              in_dim, uint32_t out_dim, uint32_t n_tokens, quest_stream_t stream) {
-    return quest_decode_norm_gemv_batched_dtype(x, gamma, eps, w, out, in_dim, out_dim, n_tokens, QUEST_DTYPE_F16, stream);
-}
-extern "C" int quest_decode_gemv_residual_batched(const void* x, const void* w, void* h, uint32_t in_dim, uint32_t out_dim,
-                                                  uint32_t n_tokens, quest_stream_t stream) {
-    return quest_decode_gemv_residual_batched_dtype(x, w, h, in_dim, out_dim, n_tokens, QUEST_DTYPE_F16, stream);
-}
-extern "C" int quest_decode_mlp_gate_up_batched(const void* h, const void* gamma, float eps, const void* w_gate, const void*
-                                                w_up, void* act, uint32_t hidden, uint32_t intermediate, uint32_t n_tokens,
-                                                quest_stream_t stream) {
-    return quest_decode_mlp_gate_up_batched_dtype(h, gamma, eps, w_gate, w_up, act, hidden, intermediate, n_tokens,
-                                                  QUEST_DTYPE_F16, stream);
-}
-extern "C" int quest_decode_qkv_rope_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk,
-                                             const void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t
-                                             num_qo_heads, uint32_t num_kv_heads, uint32_t head_dim, float rope_scale, float
-                                             rope_theta, const float* inv_freq, float attention_factor, const
-                                             quest_step_state_t* states, uint32_t n_tokens, quest_stream_t stream) {
-    return quest_decode_qkv_rope_batched_dtype(h, gamma, eps, wq, wk, wv, q, k, v, hidden, num_qo_heads, num_kv_heads,
-                                               head_dim, rope_scale, rope_theta, inv_freq, attention_factor, states, n_tokens,
-                                               QUEST_DTYPE_F16, stream);
-}
-extern "C" int quest_decode_qkv_batched(const void* h, const void* gamma, float eps, const void* wq, const void* wk, const
-                                        void* wv, void* q, void* k, void* v, uint32_t hidden, uint32_t q_rows, uint32_t
-                                        kv_rows, uint32_t n_tokens, quest_stream_t stream) {
-    return quest_decode_qkv_batched_dtype(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows, n_tokens,
-                                          QUEST_DTYPE_F16, stream);
+    return qkv(h, gamma, eps, wq, wk, wv, q, k, v, hidden, q_rows, kv_rows, true, n_tokens, dtype, stream);
 }
 
 // Which kernel an n-token launch of this shape takes, whatever its element type (both are 16 bits wide: the plan has no

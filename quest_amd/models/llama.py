@@ -12,6 +12,7 @@ plumbing, gradient checkpointing) is out of scope.  Batch size 1, like the refer
 from __future__ import annotations
 
 from dataclasses import dataclass
+from types import SimpleNamespace
 from typing import Optional
 
 import torch
@@ -154,38 +155,39 @@ class LlamaDecoderLayer(nn.Module):
         per batch: persist_kernel) -- different kernels, whose results differ in the last bits."""
         a, m = self.self_attn, self.mlp
         launches = _fused_layer_launches(controller)
-        qkv_rope, qkv_rope_freqs, gemv_residual, mlp_gate_up = launches[:4]
         freqs = a.rotary(h.device)
         qkv = (h, self.input_layernorm.weight, self.input_layernorm.variance_epsilon, a.q_proj.weight, a.k_proj.weight,
                a.v_proj.weight, ws.q, ws.k, ws.v)
         if a.qk_norm:
-            launches[5](*qkv)
+            launches.qkv(*qkv)
             qutils.apply_qk_norm_rope_in_place(ws.q, ws.k, 0, *a.qk_norm_args(), rope_scale=a.rope_scale,
                                                rope_theta=a.rope_theta, rope_freqs=freqs, states=controller.step_states)
         elif freqs is None:
-            qkv_rope(*qkv, a.head_dim, a.rope_scale, a.rope_theta, controller.step_states)
+            launches.qkv_rope(*qkv, a.head_dim, a.rope_scale, a.rope_theta, controller.step_states)
         else:
-            qkv_rope_freqs(*qkv, a.head_dim, freqs[0], freqs[1], controller.step_states)
+            launches.qkv_rope_freqs(*qkv, a.head_dim, freqs[0], freqs[1], controller.step_states)
         if dense:
             attn = qutils.decode_layer_dense_batched(ws.q, ws.k, ws.v, controller, a.layer_idx, out=ws.attn)
         else:
             attn = qutils.decode_layer_batched(ws.q, ws.k, ws.v, controller, a.layer_idx, scores, out=ws.attn)
-        gemv_residual(attn, a.o_proj.weight, h)
-        mlp_gate_up(h, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon,
-                    m.gate_proj.weight, m.up_proj.weight, ws.act)
-        gemv_residual(ws.act, m.down_proj.weight, h)
+        launches.gemv_residual(attn, a.o_proj.weight, h)
+        launches.mlp_gate_up(h, self.post_attention_layernorm.weight, self.post_attention_layernorm.variance_epsilon,
+                             m.gate_proj.weight, m.up_proj.weight, ws.act)
+        launches.gemv_residual(ws.act, m.down_proj.weight, h)
         return h
 
 
 def _fused_layer_launches(controller):
-    """The projection launches of the fused decoder layer and of the final norm + lm_head for ``controller``'s kind: (q/k/v
-    + RoPE by formula, by frequency table, GEMV + residual, MLP gate/up, norm + GEMV, q/k/v unrotated)."""
+    """The projection launches of the fused decoder layer and of the final norm + lm_head for ``controller``'s kind, by name:
+    a ``BatchedInferenceController`` takes the n-token form of each at every n, an ``InferenceController`` the one-token form.
+    (Looked up in ``_kernels`` per call, so that a test can wrap the functions there.)"""
+    k = _kernels
     if isinstance(controller, qutils.BatchedInferenceController):
-        return (_kernels.decode_qkv_rope_batched, _kernels.decode_qkv_rope_batched_freqs,
-                _kernels.decode_gemv_residual_batched, _kernels.decode_mlp_gate_up_batched, _kernels.decode_norm_gemv_batched,
-                _kernels.decode_qkv_batched)
-    return (_kernels.decode_qkv_rope, _kernels.decode_qkv_rope_freqs, _kernels.decode_gemv_residual,
-            _kernels.decode_mlp_gate_up, _kernels.decode_norm_gemv, _kernels.decode_qkv)
+        return SimpleNamespace(qkv_rope=k.decode_qkv_rope_batched, qkv_rope_freqs=k.decode_qkv_rope_batched_freqs,
+                               qkv=k.decode_qkv_batched, gemv_residual=k.decode_gemv_residual_batched,
+                               mlp_gate_up=k.decode_mlp_gate_up_batched, norm_gemv=k.decode_norm_gemv_batched)
+    return SimpleNamespace(qkv_rope=k.decode_qkv_rope, qkv_rope_freqs=k.decode_qkv_rope_freqs, qkv=k.decode_qkv,
+                           gemv_residual=k.decode_gemv_residual, mlp_gate_up=k.decode_mlp_gate_up, norm_gemv=k.decode_norm_gemv)
 
 
 def fused_layer_launches_supported(config, n_tokens: int) -> bool:
@@ -467,7 +469,7 @@ class LlamaForCausalLM(nn.Module):
             # (kept on self: the captured launches hold these buffers' addresses)
             ws = self._graph_ws = DecodeWorkspace(self.config, dtype, dev, n)
             logits = torch.empty(n, 1, self.config.vocab_size, dtype=dtype, device=dev)
-            norm_gemv = _fused_layer_launches(ctl)[4]
+            norm_gemv = _fused_layer_launches(ctl).norm_gemv
 
             def forward():
                 hs = m.forward_decode_fused(self.graph_input, self._graph_scores, ctl, ws)

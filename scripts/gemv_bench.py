@@ -8,7 +8,7 @@ tokens, RoPE formula (rope_scale / rope_theta) vs the llama3 frequency table, al
 With --qk-norm-ab: Qwen3-8B shapes (hidden 4096, 32 / 8 heads of 128), batch 1 and 8 tokens: the rotating q/k/v launch
 (frequency table) beside the unrotated one (quest_decode_qkv*) and the per-head q/k norm + RoPE launch that follows it,
 alternating A B A B.
-With --dtype bf16 (default f16): every tensor of the runs above in that element type (the <name>_dtype entries).
+With --dtype bf16 (default f16): every tensor of the runs above in that element type (the entries' dtype argument).
 With --dtype-ab: fp16 against bf16 in ONE process, alternating A B A B, the four launches of a layer at Llama-2-7B and
 Qwen3-8B shapes at 1, 4, 8 and 16 tokens: per launch the four times of each type, the medians, the fp16 runs' own spread
 (max - min) and the difference of the medians.  The bytes are the same; a difference inside the spread is none."""

@@ -145,24 +145,25 @@ def test_typed_entries_refuse_an_unknown_dtype_and_shapes_like_fp16():
     calls = _typed_calls()
     assert len(calls) == 10
     for name, (args, n) in calls.items():
-        typed, untyped = getattr(lib, name + "_dtype"), getattr(lib, name)
-        assert SIGNATURES[name + "_dtype"][1] == SIGNATURES[name][1][:-1] + [ctypes.c_uint32, ctypes.c_void_p], name
+        # one entry per operator and form: no <name>_dtype twin, dtype in front of the stream
+        assert not hasattr(lib, name + "_dtype") and name + "_dtype" not in SIGNATURES, name
+        assert SIGNATURES[name][1][-2:] == [ctypes.c_uint32, ctypes.c_void_p], name
+        entry = getattr(lib, name)
         for bad in (2, 3, 0xFFFFFFFF):
-            assert typed(*args, *n, bad, None) == EINVAL, (name, bad)
-        # a null operand: EINVAL whatever the type, as from the untyped symbol
+            assert entry(*args, *n, bad, None) == EINVAL, (name, bad)
+        # a null operand: EINVAL whatever the type
         null = (None,) + args[1:]
-        assert untyped(*null, *n, None) == EINVAL and typed(*null, *n, F16, None) == EINVAL and typed(*null, *n, BF16, None) == EINVAL, name
-    # shapes fp16 refuses with QUEST_EUNSUPPORTED are refused for bf16, and by the untyped symbol: in_dim % 8 != 0
+        assert entry(*null, *n, F16, None) == EINVAL and entry(*null, *n, BF16, None) == EINVAL, name
+    # shapes fp16 refuses with QUEST_EUNSUPPORTED are refused for bf16: in_dim % 8 != 0
     for name, (args, n) in _typed_calls(in_dim=68).items():
-        typed, untyped = getattr(lib, name + "_dtype"), getattr(lib, name)
-        got = (untyped(*args, *n, None), typed(*args, *n, F16, None), typed(*args, *n, BF16, None))
-        assert got == (EUNSUPPORTED,) * 3, (name, got)
+        entry = getattr(lib, name)
+        got = (entry(*args, *n, F16, None), entry(*args, *n, BF16, None))
+        assert got == (EUNSUPPORTED,) * 2, (name, got)
     # more than 16 tokens: EINVAL from the n-token entries of both types
     for name, (args, n) in _typed_calls().items():
         if n:
-            typed = getattr(lib, name + "_dtype")
-            assert typed(*args, 17, F16, None) == EINVAL and typed(*args, 17, BF16, None) == EINVAL, name
-            assert getattr(lib, name)(*args, 17, None) == EINVAL, name
+            entry = getattr(lib, name)
+            assert entry(*args, 17, F16, None) == EINVAL and entry(*args, 17, BF16, None) == EINVAL, name
 
 
 def test_wrappers_take_one_element_type_per_call(monkeypatch):

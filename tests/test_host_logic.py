@@ -433,26 +433,27 @@ def test_round3_entry_points_validate_arguments_without_gpu():
     assert lib.quest_decode_last_launch_info(h, info) == 0 and list(info) == [0] * 6  # nothing launched yet
     assert lib.quest_decode_last_launch_info(None, info) == -1
     lib.quest_decode_handler_destroy(h)
-    # fused decoder-layer launches
-    assert lib.quest_decode_norm_gemv(None, None, 0.0, one, one, 64, 8, None) == -1
-    assert lib.quest_decode_norm_gemv(one, None, 0.0, one, one, 60, 8, None) == -2          # in_dim % 8
-    assert lib.quest_decode_gemv_residual(one, one, None, 64, 8, None) == -1
-    assert lib.quest_decode_mlp_gate_up(one, None, 1e-5, one, one, one, 64, 128, None) == -1  # the MLP launch needs gamma
-    assert lib.quest_decode_qkv_rope(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 1.0, 1e4, None, 1.0, None,
-                                     None) == -1
-    assert lib.quest_decode_qkv_rope(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 0.0, 1e4, None, 1.0, one,
-                                     None) == -1
-    # ... and their n-token forms: 1..16 tokens, same argument rules (checked before anything is launched)
-    assert lib.quest_decode_norm_gemv_batched(None, None, 0.0, one, one, 64, 8, 8, None) == -1
-    assert lib.quest_decode_norm_gemv_batched(one, None, 0.0, one, one, 64, 8, 0, None) == -1
-    assert lib.quest_decode_norm_gemv_batched(one, None, 0.0, one, one, 64, 8, 17, None) == -1
-    assert lib.quest_decode_norm_gemv_batched(one, None, 0.0, one, one, 60, 8, 8, None) == -2   # in_dim % 8
-    assert lib.quest_decode_gemv_residual_batched(one, one, None, 64, 8, 8, None) == -1
-    assert lib.quest_decode_mlp_gate_up_batched(one, None, 1e-5, one, one, one, 64, 128, 8, None) == -1
-    assert lib.quest_decode_qkv_rope_batched(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 1.0, 1e4, None, 1.0, None, 8,
-                                             None) == -1
-    assert lib.quest_decode_qkv_rope_batched(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 72, 1.0, 1e4, None, 1.0, one, 8,
-                                             None) == -2   # head_dim % 16
+    # fused decoder-layer launches: the same refusals for both element types (QUEST_DTYPE_F16 = 0, QUEST_DTYPE_BF16 = 1)
+    for dt in (0, 1):
+        assert lib.quest_decode_norm_gemv(None, None, 0.0, one, one, 64, 8, dt, None) == -1
+        assert lib.quest_decode_norm_gemv(one, None, 0.0, one, one, 60, 8, dt, None) == -2          # in_dim % 8
+        assert lib.quest_decode_gemv_residual(one, one, None, 64, 8, dt, None) == -1
+        assert lib.quest_decode_mlp_gate_up(one, None, 1e-5, one, one, one, 64, 128, dt, None) == -1  # the MLP launch needs gamma
+        assert lib.quest_decode_qkv_rope(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 1.0, 1e4, None, 1.0, None,
+                                         dt, None) == -1
+        assert lib.quest_decode_qkv_rope(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 0.0, 1e4, None, 1.0, one,
+                                         dt, None) == -1
+        # ... and their n-token forms: 1..16 tokens, same argument rules (checked before anything is launched)
+        assert lib.quest_decode_norm_gemv_batched(None, None, 0.0, one, one, 64, 8, 8, dt, None) == -1
+        assert lib.quest_decode_norm_gemv_batched(one, None, 0.0, one, one, 64, 8, 0, dt, None) == -1
+        assert lib.quest_decode_norm_gemv_batched(one, None, 0.0, one, one, 64, 8, 17, dt, None) == -1
+        assert lib.quest_decode_norm_gemv_batched(one, None, 0.0, one, one, 60, 8, 8, dt, None) == -2   # in_dim % 8
+        assert lib.quest_decode_gemv_residual_batched(one, one, None, 64, 8, 8, dt, None) == -1
+        assert lib.quest_decode_mlp_gate_up_batched(one, None, 1e-5, one, one, one, 64, 128, 8, dt, None) == -1
+        assert lib.quest_decode_qkv_rope_batched(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 128, 1.0, 1e4, None, 1.0,
+                                                 None, 8, dt, None) == -1
+        assert lib.quest_decode_qkv_rope_batched(one, one, 1e-5, one, one, one, one, one, one, 512, 4, 4, 72, 1.0, 1e4, None, 1.0,
+                                                 one, 8, dt, None) == -2   # head_dim % 16
     assert lib.quest_build_info().startswith(b"quest_hip gfx950 src=")
 
 

@@ -190,8 +190,8 @@ def test_new_symbols_are_exported_and_declared():
     from quest_amd._lib import SIGNATURES, lib
 
     header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "quest_hip.h")).read()
-    for name, n_args in (("quest_apply_qk_norm_rope_in_place_dtype", 17), ("quest_decode_qkv", 13),
-                         ("quest_decode_qkv_batched", 14)):
+    for name, n_args in (("quest_apply_qk_norm_rope_in_place_dtype", 17), ("quest_decode_qkv", 14),
+                         ("quest_decode_qkv_batched", 15)):
         assert hasattr(lib, name) and len(SIGNATURES[name][1]) == n_args
         assert f"int {name}(" in header
     for fn in ("apply_qk_norm_rope_in_place", "decode_qkv", "decode_qkv_batched"):
@@ -235,7 +235,7 @@ def _qkv(batched, **kw):
     a = dict(h=ONE, gamma=ONE, eps=1e-6, wq=ONE, wk=ONE, wv=ONE, q=ONE, k=ONE, v=ONE, hidden=4096, q_rows=4096, kv_rows=1024)
     if batched:
         a["n"] = 8
-    a["stream"] = None
+    a["dtype"], a["stream"] = 0, None  # QUEST_DTYPE_F16
     a.update(kw)
     return list(a.values())
 

@@ -190,20 +190,20 @@ def test_c_entries_refuse_a_missing_table_or_a_bad_attention_factor():
     tensor pointers: nothing is dereferenced on these paths.)"""
     from quest_amd._lib import lib
 
-    EINVAL = -1
+    EINVAL, F16 = -1, 0  # QUEST_EINVAL, QUEST_DTYPE_F16
     assert lib.quest_error_string(EINVAL).decode()
     p = ctypes.c_void_p(16)
     table = ctypes.c_void_p(64)
     for tab, f in ((None, 1.0), (table, 0.0), (table, -1.0), (table, float("nan")), (table, float("inf"))):
         assert lib.quest_apply_rope_in_place_dtype(p, p, 1, 0, 4, 4, 128, 0.0, 0.0, tab, f, None, 0, None) == EINVAL
         assert lib.quest_apply_rope_in_place_dtype(p, p, 1, 0, 4, 4, 128, 0.0, 0.0, tab, f, p, 0, None) == EINVAL
-        assert lib.quest_decode_qkv_rope(p, p, 1e-5, p, p, p, p, p, p, 512, 4, 4, 128, 0.0, 0.0, tab, f, p, None) == EINVAL
+        assert lib.quest_decode_qkv_rope(p, p, 1e-5, p, p, p, p, p, p, 512, 4, 4, 128, 0.0, 0.0, tab, f, p, F16, None) == EINVAL
         assert lib.quest_decode_qkv_rope_batched(p, p, 1e-5, p, p, p, p, p, p, 512, 4, 4, 128, 0.0, 0.0, tab, f, p, 2,
-                                                 None) == EINVAL
+                                                 F16, None) == EINVAL
     # head-dim rules of the existing entries (checked before any launch as well); n == 0 launches nothing
     assert lib.quest_apply_rope_in_place_dtype(p, p, 1, 0, 4, 4, 96, 0.0, 0.0, table, 1.0, None, 0, None) < 0
     assert lib.quest_apply_rope_in_place_dtype(p, p, 0, 0, 4, 4, 128, 0.0, 0.0, table, 1.0, None, 0, None) == 0
     assert lib.quest_apply_rope_in_place_dtype(None, p, 1, 0, 4, 4, 128, 0.0, 0.0, table, 1.0, None, 0, None) == EINVAL
-    assert lib.quest_decode_qkv_rope(p, p, 1e-5, p, p, p, p, p, p, 512, 4, 4, 130, 0.0, 0.0, table, 1.0, p, None) < 0
+    assert lib.quest_decode_qkv_rope(p, p, 1e-5, p, p, p, p, p, p, 512, 4, 4, 130, 0.0, 0.0, table, 1.0, p, F16, None) < 0
     assert lib.quest_decode_qkv_rope_batched(p, p, 1e-5, p, p, p, p, p, p, 512, 4, 4, 72, 0.0, 0.0, table, 1.0, p, 2,
-                                             None) < 0
+                                             F16, None) < 0
